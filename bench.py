@@ -28,8 +28,16 @@ max over ranks.
 device list (`--gpus N`: devices 0..N-1; SCC_BENCH_DEVICES="0,0" rehearses a
 two-entry list on one GPU), the DE's gene blocks and the distance's column
 slices spread over the list inside libscc (peer copies, no RCCL).  Under a
-multi-rank launch (the driver's `--gpus N` runs) rank 0 also times this route
-over all N GPUs after the rank route and reports it as "route_devices".
+multi-rank launch with `--full` rank 0 also times this route over all N GPUs
+after the rank route and reports it as "route_devices".
+
+A plain run sets up, warms up (every stage timed: the per-stage table), times
+`--steps` steps and prints the result line.  `--full` adds the side
+measurements: the CPU baseline, the D2H / H2D transfer and cold-call times,
+the Pearson kernel, config E's repeated dataset builds and the device-list
+route beside a multi-rank run.  `--dump-outputs DIR` writes what the last
+timed step left its caller as DIR/<name>.npy; the inputs are seeded by the
+config, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -74,7 +82,48 @@ def _args(argv=None):
                          "list inside libscc (the R drop-in's nCores route)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only: the launcher / rank / timing path with a placeholder step (tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: the CPU baseline, the D2H / H2D transfers and the cold call, "
+                         "the Pearson kernel, config E's repeated dataset builds, the device-list route beside a "
+                         "multi-rank run (each still has its --no-... switch); without it: set up, warm up, time "
+                         "the steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
+    a = ap.parse_args(argv)
+    if not a.full:
+        a.no_cpu_baseline = a.no_pearson = a.no_transfers = True
+    return a
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as path/<name>.npy in float64.  Past DUMP_BYTES in
+    all, each array larger than its equal share of the budget is cut to a
+    fixed, seeded sample of its (flattened) entries, in index order."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // (8 * len(arrays))
+        for k, v in arrays.items():
+            if v.size > share:
+                idx = np.sort(np.random.default_rng(12345).choice(v.size, share, replace=False))
+                arrays[k] = v.reshape(-1)[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def de_result_arrays(r):
+    """The arrays of a DeResult as the step fetched it (the union; the tested
+    rows too when the step fetched them)."""
+    out = {"union": r.union}
+    if r.rows is not None:
+        rw = r.rows
+        out.update({"pair_tested": rw.pair_tested, "row_gene": rw.gene, "row_p": rw.p, "row_q": rw.q,
+                    "row_avg_logfc": rw.avg_logfc, "row_pct1": rw.pct1, "row_pct2": rw.pct2, "row_u2": rw.u2,
+                    "row_ties": rw.ties, "row_de": rw.de, "row_top": rw.top})
+    return out
 
 
 def _free_port():
@@ -94,6 +143,49 @@ def launch_ranks(a) -> int:
 
 
 DEVICE_GEN = ("C", "D", "E")
+
+# synth.generate draws one serial numpy stream: half a minute at config B.
+# Its output is kept here between runs (build() fills it for the headline
+# config), keyed by the config, the seed and the generator's source.
+INPUT_CACHE = os.path.join(ROOT, ".bench_cache")
+
+
+def _input_cache_path(config, seed):
+    import hashlib
+
+    from scconsensus_amd import synth
+    with open(synth.__file__, "rb") as f:
+        tag = hashlib.sha256(f.read()).hexdigest()[:16]
+    return os.path.join(INPUT_CACHE, f"synth_{config}_seed{seed}_{tag}.npz")
+
+
+def host_dataset(config, seed):
+    """synth.generate(config, seed=seed), read back from INPUT_CACHE when an
+    earlier call left it there (the same arrays, bit for bit)."""
+    from scconsensus_amd import synth
+    path = _input_cache_path(config, seed)
+    if os.path.exists(path):
+        with np.load(path) as z:
+            G, N = int(z["shape"][0]), int(z["shape"][1])
+            return synth.Dataset(G, N, z["indptr"], z["indices"], z["data"], z["labels"].astype(object),
+                                 [f"gene{g:05d}" for g in range(G)], [f"cell{c:07d}" for c in range(N)])
+    d = synth.generate(config, seed=seed)
+    tmp = f"{path}.{os.getpid()}.tmp.npz"
+    try:  # the cache is an optimisation: a tree that cannot be written to still runs
+        os.makedirs(INPUT_CACHE, exist_ok=True)
+        np.savez(tmp, shape=np.array([d.G, d.N], np.int64), indptr=d.indptr, indices=d.indices, data=d.data,
+                 labels=d.labels.astype(str))
+        os.replace(tmp, path)
+    except OSError:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return d
+
+
+def prepare_inputs(config="B"):
+    """Fill INPUT_CACHE for a host-generated config (called by build())."""
+    from scconsensus_amd.synth import CONFIGS
+    host_dataset(config, CONFIGS[config]["seed"])
 
 
 def cpu_baseline(d, code, K, union, sample_genes, seed=0):
@@ -225,6 +317,8 @@ def de_only(a, eng, ds, d, code, K, dist, world, dataset_ms=None):
     dist.barrier()
     dt = dist.max_over_ranks(time.perf_counter() - t0)
     s_step = dt / a.steps
+    if a.dump_outputs and dist.rank == 0:
+        dump_outputs(a.dump_outputs, de_result_arrays(r))
     fams = ["ingest", "gene_stats", "pair_filter", "gene_rank", "pair_test", "pair_select"]
     stage_ms = {}
     for f in fams:
@@ -397,7 +491,7 @@ def main():
         d = synth.generate_device(a.config, f"cuda:{gpu}", seed=seed, layout="csr" if a.config == "E" else "csc")
         torch.cuda.synchronize()
     else:
-        d = synth.generate(a.config, seed=seed)
+        d = host_dataset(a.config, seed)
     names, code = api.select_clusters(d.labels, 10)
     K = len(names)
     P = K * (K - 1) // 2
@@ -408,24 +502,28 @@ def main():
         # dataset is created (k_ct_bounds / k_ct_tiles / k_ct_pass1 / k_ct_pass2): an R call on a
         # dgRMatrix pays it once per call, so it is timed and reported beside
         # the DE (first build: allocations; then the mean of repeated builds)
+        # (--full; a plain run builds the dataset once and reports the DE alone)
         build = []
-        for i in range(3):
+        nbuild = 3 if a.full else 1
+        for i in range(nbuild):
             eng.synchronize()
             t0 = time.perf_counter()
             ds = eng.dataset_csr_device(d.indptr.data_ptr(), d.indices.data_ptr(), d.data.data_ptr(), d.G, d.N,
                                         d.nnz)
             eng.synchronize()
             build.append((time.perf_counter() - t0) * 1e3)
-            if i < 2:
+            if i < nbuild - 1:
                 ds.close()
-        return de_only(a, eng, ds, d, code, K, dist, world, dataset_ms=build)
+        return de_only(a, eng, ds, d, code, K, dist, world, dataset_ms=build if a.full else None)
     if a.config in DEVICE_GEN:
         ds = eng.dataset_csc_device(d.indptr.data_ptr(), d.indices.data_ptr(), d.data.data_ptr(), d.G, d.N, d.nnz)
+    elif a.no_transfers:
+        ds = eng.dataset_csc(d.indptr, d.indices, d.data, d.G, d.N)  # input H2D: before the timed region
     else:
         ds = eng.dataset_csc(d.indptr, d.indices, d.data, d.G, d.N)  # warm-up upload (allocations, first touch)
         ds.close()
         t0 = time.perf_counter()
-        ds = eng.dataset_csc(d.indptr, d.indices, d.data, d.G, d.N)  # input H2D: before the timed region
+        ds = eng.dataset_csc(d.indptr, d.indices, d.data, d.G, d.N)  # input H2D: timed, before the timed region
         h2d_ms = (time.perf_counter() - t0) * 1e3
     npairs_cells = d.N * (d.N - 1) / 2
     multi = shard and world > 1
@@ -543,6 +641,18 @@ def main():
     stage_ms_warmup_dom = stage_ms[dom]
     stage_ms[dom] = t_dom[0] / max(t_dom[1], 1)
     os.environ["SCC_PROFILE_STAGES"] = "-"  # the side measurements below: no stage events
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left its caller: the DE result it returned
+        # and the distance the engine keeps in HBM.  That copy is read only by
+        # later calls on the context, so it is written as what those return:
+        # the PCA scores it was formed from and the silhouette widths of the
+        # compared clusters over it (every packed entry enters them).  A
+        # multi-rank job keeps only column slices: the DE result alone.
+        arrays = de_result_arrays(r)
+        if not multi:
+            arrays["pca_scores"] = eng.last_pca_scores(d.N)
+            arrays["dist_silhouette_widths"] = eng.silhouette(d.N, code)[0]
+        dump_outputs(a.dump_outputs, arrays)
     traffic = None
     # counters of THIS DE mode only (a SLOW line never borrows FAST's kernels' traffic)
     ttag = a.config + ("_slow" if a.de == "slow" else "")
@@ -637,7 +747,7 @@ def main():
     jobs = world if not shard else 1
     value = jobs * npairs_cells / (ms / 1e3)
     side_devices = None
-    if world > 1 and shard and a.config in ("A", "B", "C", "D"):
+    if a.full and world > 1 and shard and a.config in ("A", "B", "C", "D"):
         # the R drop-in's route over the same N GPUs: rank 0 alone drives a
         # device list [0 .. N-1] (the other ranks wait at the barrier)
         dist.barrier()

@@ -16,6 +16,6 @@ grep "scc rank" gpurun_out/cfg/$n.err | tail -1; }
 SCC_RANK_LOG=1 run B 300 python bench.py --no-cpu-baseline --no-transfers --no-pearson --steps 10 --warmup 3
 SCC_RANK_LOG=1 run C 400 python bench.py --config C --no-cpu-baseline --no-transfers --no-pearson --steps 3 --warmup 2
 SCC_RANK_LOG=1 run D 400 python bench.py --config D --no-cpu-baseline --no-transfers --no-pearson --steps 3 --warmup 2
-SCC_RANK_LOG=1 run E 400 python bench.py --config E --no-cpu-baseline --steps 3 --warmup 1
+SCC_RANK_LOG=1 run E 400 python bench.py --full --config E --no-cpu-baseline --steps 3 --warmup 1
 SCC_RANK_LOG=1 run Dslow 400 python bench.py --config D --de slow --no-cpu-baseline --no-transfers --no-pearson --steps 2 --warmup 1
 SCC_RANK_LOG=1 run Bslow 300 python bench.py --de slow --no-cpu-baseline --no-transfers --no-pearson --steps 10 --warmup 3

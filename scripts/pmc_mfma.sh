@@ -10,7 +10,7 @@ out=gpurun_out/pmc_mfma
 mkdir -p $out
 run() {  # name, counters, bench args
   timeout -s KILL 240 rocprofv3 --pmc $2 --output-format csv -d $out/$1 -o run -- \
-    python3 bench.py --no-cpu-baseline --no-transfers --steps 2 --warmup 1 $3 > $out/$1.log 2>&1
+    python3 bench.py --full --no-cpu-baseline --no-transfers --steps 2 --warmup 1 $3 > $out/$1.log 2>&1
   rc=$?; echo "pass $1 rc=$rc"
   return $rc
 }
