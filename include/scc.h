@@ -51,6 +51,31 @@ extern "C" {
 #define SCC_DE_SLOW 1 /* reclusterDEConsensus(method = "Wilcoxon") */
 #define SCC_TEST_WILCOX 0 /* FAST test.use = "wilcox" (WilcoxDETest, Fast:78-91) */
 #define SCC_TEST_T 1      /* FAST test.use = "t" (DiffTTest: Welch t.test, Fast:185-196) */
+#define SCC_TEST_BIMOD 2  /* FAST test.use = "bimod" (DiffExpTest: McDavid's zero-inflated LRT, Fast:93-133) */
+/* test.use = "roc" has no defined result (the caller filters on p_val_adj, which
+ * the roc branch never produces, Fast:343-351,377) and is not offered.
+ *
+ * SCC_TEST_BIMOD, per tested (pair, gene): for a group of n cells with the
+ * n2 values x2 = x[x > 0] (zeros and negative values are the other part, n1),
+ *   xal = min(max(n2 / n, 1e-5), 1 - 1e-5)
+ *   sd  = 1 if n2 < 2, else sd(x2) (two-pass, divisor n2 - 1)
+ *   lik = n1 log(1 - xal) + n2 log(xal) + sum(dnorm(x2, mean(x2), sd, log = TRUE))
+ *   lrt = 2 (lik(x) + lik(y) - lik(c(x, y)));  p = pchisq(lrt, df = 3, lower.tail = FALSE)
+ * from per-(gene, cluster) moments of the values > 0 (count, mean, two-pass sum
+ * of squared deviations, minimum, maximum); the pooled group's by Chan's merge.
+ * R's IEEE cases are decided explicitly, not left to rounding:
+ *   - n2 >= 2 values that are all equal (minimum == maximum bitwise): sd = 0,
+ *     dnorm(x, x, 0, log = TRUE) = +Inf, lik = +Inf;
+ *   - lrt <= 0 (-Inf included): p = 1;  lrt = +Inf: p = 0;
+ *   - lrt = Inf - Inf = NaN: p = NaN.  R turns it into an NA p_val_adj, an
+ *     all-NA marker row, an NA in deGeneUnion, and stops at
+ *     dataMatrix[deGeneUnion, ]: the run fails with SCC_ERR_RSTOP, for cells
+ *     the pair tests only (cells computed because test_all is set never fail
+ *     a run).  One deviation: R does not stop when the affected pair has that
+ *     single tested row (a pair with <= 1 row contributes nothing, Fast:376);
+ *     the engine stops there as well.
+ * u2 and ties are 0, as for SCC_TEST_T; the feature filters, BH, top_n and the
+ * union do not depend on the test. */
 
 #define SCC_DIST_PCA_EUCLID 0 /* dist(prcomp_irlba(t(X[U,]), n=min(|U|,15))$x) */
 #define SCC_DIST_PEARSON 1    /* as.dist(1 - cor(X[U,], method = "pearson")) */
@@ -82,7 +107,8 @@ typedef struct {
     double mean_scaling_factor; /* SLOW: meanScalingFactor (slow:23) */
     int32_t test_all;           /* FAST: 1 = also compute U / p for the (pair, gene) cells the
                                    feature filters drop (diagnostics; R never tests them) */
-    int32_t test;               /* FAST: SCC_TEST_WILCOX (default) | SCC_TEST_T; u2 / ties are 0 for t */
+    int32_t test;               /* FAST: SCC_TEST_WILCOX (default) | SCC_TEST_T | SCC_TEST_BIMOD; u2 / ties
+                                   are 0 for t and bimod.  SLOW takes SCC_TEST_WILCOX only */
 } scc_de_params;
 
 /* ---- context ---------------------------------------------------------- */

@@ -92,9 +92,10 @@ reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method 
                                      minClusterSize = 10, minPerCent = 20,
                                      filename = "de_gene_object.rds", plotName = "DE_Heatmap",
                                      NumbertopDEGenes = 30, nCores = 1) {
-  # test.use = method (Fast:372): "wilcox" and "t" run on the engine; "bimod" /
-  # "roc" need Seurat helpers the reference never loads
-  if (!(method %in% c("wilcox", "t"))) stop("Unknown test: ", method)
+  # test.use = method (Fast:372): "wilcox", "t" and "bimod" run on the engine
+  # (SCC_TEST_* codes 0, 1, 2); "roc" yields no p_val_adj, which Fast:377 filters on
+  tests <- c("wilcox", "t", "bimod")
+  if (!(method %in% tests)) stop("Unknown test: ", method)
   sel <- .scc_codes(consensusClusterLabels, dataMatrix, minClusterSize)
   # nCores PSOCK workers (Fast:61-65) -> min(nCores, GPUs) devices of ONE sharded job
   .Call("C_scc_devices", as.integer(nCores))
@@ -102,7 +103,7 @@ reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method 
   on.exit(.Call("C_scc_release", h), add = TRUE)
   res <- .Call("C_scc_de_fast", h, sel$code, length(sel$clusters),
                as.double(qValThrs), as.double(logFCThrs), as.double(minPerCent),
-               as.integer(NumbertopDEGenes), as.integer(method == "t"))
+               as.integer(NumbertopDEGenes), match(method, tests) - 1L)
   deGeneUnion <- rownames(dataMatrix)[res[[1]]]
   print(str(deGeneUnion))
   d <- .scc_dist(h, res[[1]], ncol(dataMatrix))

@@ -136,7 +136,7 @@ SEXP C_scc_release(SEXP h)
 }
 
 /* returns list(union = int (1-based gene rows), nodg = int[N]) */
-SEXP C_scc_de_fast(SEXP h, SEXP code, SEXP K, SEXP qthr, SEXP lfc, SEXP minpct, SEXP topn, SEXP ttest)
+SEXP C_scc_de_fast(SEXP h, SEXP code, SEXP K, SEXP qthr, SEXP lfc, SEXP minpct, SEXP topn, SEXP test)
 {
     ensure_ctx();
     int N = 0;
@@ -149,7 +149,9 @@ SEXP C_scc_de_fast(SEXP h, SEXP code, SEXP K, SEXP qthr, SEXP lfc, SEXP minpct, 
     prm.log_fc_thrs = Rf_asReal(lfc);
     prm.min_per_cent = Rf_asReal(minpct);
     prm.top_n = Rf_asInteger(topn);
-    prm.test = Rf_asInteger(ttest) ? SCC_TEST_T : SCC_TEST_WILCOX; /* test.use = method (Fast:372) */
+    /* test.use = method (Fast:372) as its SCC_TEST_* code: 0 wilcox, 1 t (the values the
+     * earlier logical "t test?" argument took), 2 bimod; the engine rejects any other */
+    prm.test = Rf_asInteger(test);
     scc_de_result* r = NULL;
     int rc = scc_de_run(g_ctx, ds, INTEGER(code), Rf_asInteger(K), &prm, &r);
     if (rc != SCC_OK && !r) check(rc);

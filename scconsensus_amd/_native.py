@@ -27,6 +27,8 @@ SCC_DE_FAST = 0
 SCC_DE_SLOW = 1
 SCC_TEST_WILCOX = 0
 SCC_TEST_T = 1
+SCC_TEST_BIMOD = 2
+_TEST_CODES = {"wilcox": SCC_TEST_WILCOX, "t": SCC_TEST_T, "bimod": SCC_TEST_BIMOD}
 SCC_DIST_PCA_EUCLID = 0
 SCC_DIST_PEARSON = 1
 SCC_PTR_HOST = 0
@@ -318,10 +320,10 @@ class Engine:
     @staticmethod
     def _de_params(mode, q_val_thrs, log_fc_thrs, min_per_cent, top_n, fc_thrs, mean_scaling_factor, test_all,
                    test="wilcox"):
-        if test not in ("wilcox", "t"):
-            raise ValueError(f"test must be 'wilcox' or 't', not {test!r}")
+        if test not in _TEST_CODES:
+            raise ValueError(f"test must be 'wilcox', 't' or 'bimod', not {test!r}")
         return DeParams(mode, top_n, q_val_thrs, log_fc_thrs, min_per_cent, fc_thrs, mean_scaling_factor,
-                        1 if test_all else 0, SCC_TEST_T if test == "t" else SCC_TEST_WILCOX)
+                        1 if test_all else 0, _TEST_CODES[test])
 
     def de_shard_bytes(self, K, G) -> int:
         return int(self.lib.scc_de_shard_bytes(K, G))

@@ -174,9 +174,10 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
                              deepSplitValues=(1, 2, 3, 4), minClusterSize=10, minPerCent=20,
                              filename="de_gene_object.rds", plotName="DE_Heatmap", NumbertopDEGenes=30, nCores=1,
                              *, gene_names=None, cluster_order=None, device=0, save=False, return_details=False):
-    if method not in ("wilcox", "t"):
-        # Fast:306-333: "bimod"/"roc" need Seurat helpers the reference never loads
-        raise NotImplementedError(f"Unknown test: {method} (this engine implements test.use = 'wilcox' and 't')")
+    if method not in ("wilcox", "t", "bimod"):
+        # Fast:306-333: "roc" yields no p_val_adj, which the caller filters on (Fast:343-351,377)
+        raise NotImplementedError(f"Unknown test: {method} (this engine implements test.use = 'wilcox', 't' "
+                                  "and 'bimod')")
     eng = _engine(device)
     m = _as_matrix(dataMatrix)
     N = m[-1] if m[0] in ("csc", "csr") else m[1].shape[1]

@@ -13,6 +13,9 @@
 #define SCC_TEST_WILCOX 0
 #define SCC_TEST_T 1
 #endif
+#ifndef SCC_TEST_BIMOD
+#define SCC_TEST_BIMOD 2
+#endif
 
 #define SCC_ING_HIST_WAVES 16  // waves per ingest histogram workgroup (one partial expm1 sum each)
 
@@ -36,10 +39,15 @@ struct ScStatsLaunch {
     double* mean_e;     // [K][G] (fast mode only)
     double* var_x;      // [K][G] (fast t test only)
     int mode;           // SCC_DE_FAST: mean of expm1(x); SCC_DE_SLOW: mean of x
-    int test;           // SCC_TEST_WILCOX | SCC_TEST_T (FAST)
+    int test;           // SCC_TEST_WILCOX | SCC_TEST_T | SCC_TEST_BIMOD (FAST)
     uint32_t* cnt_pos;  // [K][G]
     uint32_t* cnt_neg;  // [K][G]
     int glo, gn;        // the genes [glo, glo + gn) (a gene shard; nothing else is read downstream)
+    // FAST bimod test only, over the values x > 0 of each (cluster, gene): [K][G]
+    double* mean_pos;   // their mean (0 when there is none)
+    double* m2_pos;     // sum((x - mean_pos)^2), second pass
+    double* min_pos;    // their minimum (+Inf when there is none)
+    double* max_pos;    // their maximum (-Inf when there is none)
 };
 
 // one unit of rank work: a whole gene (src 0: the ingest's cluster-grouped
@@ -120,9 +128,14 @@ struct ScTestLaunch {
     const unsigned long long* accX;
     const unsigned long long* accF;
     int all_pairs;
-    int test;              // SCC_TEST_WILCOX | SCC_TEST_T
+    int test;              // SCC_TEST_WILCOX | SCC_TEST_T | SCC_TEST_BIMOD
     const double* var_x;   // [K][G] (t test)
-    int* err;              // bit 8: t.test would stop ("data are essentially constant")
+    const double* mean_pos;  // [K][G] moments of the values x > 0 (bimod test, ScStatsLaunch)
+    const double* m2_pos;
+    const double* min_pos;
+    const double* max_pos;
+    int* err;              // bit 8: t.test would stop ("data are essentially constant");
+                           // bit 0x20: the bimod p of a tested cell is NaN (R stops downstream)
     const double* wtab;
     const int* woff;
     double* out_p;

@@ -529,6 +529,10 @@ struct RecIO {  // the compact exchange's buffers (DE_SHARD_REC out, DE_FINISH_R
 static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_t K, const scc_de_params* prm,
                        int stage, int64_t glo64, int64_t ghi64, void* shard, scc_de_result** out,
                        const RecIO* rio);
+// error-word bit 0x20 (k_pair_test): the bimod p of a cell its pair tests is NaN
+static const char kBimodNaN[] =
+    "bimod: the p-value of a tested gene is NaN (constant positive values in both clusters and pooled: "
+    "lrt = Inf - Inf); R's NA p_val_adj ends in stop() at dataMatrix[deGeneUnion, ]";
 extern "C" void scc_rank_split_diag(hipStream_t st, int ngenes);
 
 static int de_run_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_t K, const scc_de_params* prm,
@@ -550,8 +554,9 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     if (out) *out = nullptr;
     if (ds->ctx != c) return fail(c, SCC_ERR_INVALID, "dataset belongs to another context");
     if (prm->mode != SCC_DE_FAST && prm->mode != SCC_DE_SLOW) return fail(c, SCC_ERR_INVALID, "bad mode");
-    if (prm->test != SCC_TEST_WILCOX && (prm->test != SCC_TEST_T || prm->mode != SCC_DE_FAST))
-        return fail(c, SCC_ERR_INVALID, "test: SCC_TEST_WILCOX, or SCC_TEST_T with SCC_DE_FAST");
+    if (prm->test != SCC_TEST_WILCOX &&
+        ((prm->test != SCC_TEST_T && prm->test != SCC_TEST_BIMOD) || prm->mode != SCC_DE_FAST))
+        return fail(c, SCC_ERR_INVALID, "test: SCC_TEST_WILCOX, or SCC_TEST_T / SCC_TEST_BIMOD with SCC_DE_FAST");
     if (K < 2) return fail(c, SCC_ERR_INVALID, "need at least two clusters");
     if (K > kMaxK)
         return fail(c, SCC_ERR_UNSUPPORTED,
@@ -681,8 +686,15 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     WS("cntpos", GK, d_cntpos);
     WS("cntneg", GK, d_cntneg);
     const bool ttest = fast && prm->test == SCC_TEST_T;  // DiffTTest (Fast:185-196): no rank stage
-    double* d_vx;
+    const bool bimod = fast && prm->test == SCC_TEST_BIMOD;  // DiffExpTest (Fast:93-133): moments of x > 0
+    const bool norank = ttest || bimod;  // both tests are functions of per-(gene, cluster) moments
+    const int test = ttest ? SCC_TEST_T : bimod ? SCC_TEST_BIMOD : SCC_TEST_WILCOX;
+    double *d_vx, *d_mpos, *d_m2pos, *d_minpos, *d_maxpos;
     WS("vx", ttest ? GK : 1, d_vx);
+    WS("mpos", bimod ? GK : 1, d_mpos);
+    WS("m2pos", bimod ? GK : 1, d_m2pos);
+    WS("minpos", bimod ? GK : 1, d_minpos);
+    WS("maxpos", bimod ? GK : 1, d_maxpos);
     // rank accumulators: S, E, X per (pair, gene), F per (cluster, gene)
     const size_t acc_n = 3 * PG + (size_t)GK;
     WS("acc", acc_n, d_acc);
@@ -786,7 +798,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     {
         Scope sc(c, "ingest", s0);
         // error words, counters, rank accumulators and first-occurrence keys in one launch
-        HIPCHK(c, scc_launch_de_clear(d_err, d_counts, ttest ? nullptr : d_acc, (long long)acc_n, d_first, (int)G, glo,
+        HIPCHK(c, scc_launch_de_clear(d_err, d_counts, norank ? nullptr : d_acc, (long long)acc_n, d_first, (int)G, glo,
                                       ghi, s0));
         de_cleared = true;
         if ((hist_rng || hist_ro) && !ds->d_tbnd) {  // once per dataset: every cell's gene-tile starts
@@ -847,8 +859,12 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
         S.cnt_pos = d_cntpos;
         S.cnt_neg = d_cntneg;
         S.mode = prm->mode;
-        S.test = ttest ? SCC_TEST_T : SCC_TEST_WILCOX;
+        S.test = test;
         S.var_x = d_vx;
+        S.mean_pos = d_mpos;
+        S.m2_pos = d_m2pos;
+        S.min_pos = d_minpos;
+        S.max_pos = d_maxpos;
         S.glo = glo;
         S.gn = ghi - glo;
         HIPCHK(c, scc_launch_gene_stats(&S, s0));
@@ -890,8 +906,12 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     T.accX = accX;
     T.accF = accF;
     T.all_pairs = all_pairs ? 1 : 0;
-    T.test = ttest ? SCC_TEST_T : SCC_TEST_WILCOX;
+    T.test = test;
     T.var_x = d_vx;
+    T.mean_pos = d_mpos;
+    T.m2_pos = d_m2pos;
+    T.min_pos = d_minpos;
+    T.max_pos = d_maxpos;
     T.err = d_err;
     T.wtab = c->d_wtab;
     T.woff = c->d_woff;
@@ -906,7 +926,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
         Scope sc(c, "pair_filter", s0);
         HIPCHK(c, scc_launch_pair_filter(&T, s0));
     }
-    if (!ttest) {
+    if (!norank) {
         Scope sc(c, "gene_rank", s0);
         if (!de_cleared) HIPCHK(c, hipMemsetAsync(d_acc, 0, sizeof(unsigned long long) * acc_n, s0));
         ScRankLaunch L{};
@@ -1110,6 +1130,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
         if (e & 2) return fail(c, SCC_ERR_INVALID, "row index out of range");
         if (e & 4) return fail(c, SCC_ERR_INVALID, "row indices not strictly increasing within a column (dgCMatrix)");
         if (e & 8) return fail(c, SCC_ERR_RSTOP, "t.test: data are essentially constant (R stop())");
+        if (e & 0x20) return fail(c, SCC_ERR_RSTOP, kBimodNaN);
         return note_validated(e);
     }
     if (stage == DE_FINISH) {
@@ -1247,6 +1268,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     if (hdr[1] & 2) return fail(c, SCC_ERR_INVALID, "row index out of range");
     if (hdr[1] & 4) return fail(c, SCC_ERR_INVALID, "row indices not strictly increasing within a column (dgCMatrix)");
     if (hdr[1] & 8) return fail(c, SCC_ERR_RSTOP, "t.test: data are essentially constant (R stop())");
+    if (hdr[1] & 0x20) return fail(c, SCC_ERR_RSTOP, kBimodNaN);
     if (hdr[1] & 16) return fail(c, SCC_ERR_INVALID, "scc_de_finish_records: record out of range");
     if ((rc = note_validated(hdr[1]))) return rc;
     scc_de_result* r = new scc_de_result();

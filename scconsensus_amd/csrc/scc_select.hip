@@ -206,6 +206,42 @@ __device__ inline double t_two_sided(double t, double n)
     return 2 * (val / 2.0);  // x <= 0: pt(x, lower) = val / 2
 }
 
+// -------------------------------------------------------- bimod LRT
+// McDavid's zero-inflated likelihood-ratio test as Seurat's DiffExpTest runs it
+// (bimodLikData / DifferentialLRT, Fast:93-133), from the sufficient statistics
+// of a group of n cells: n2 values x > 0 with sum of squared deviations m2 about
+// their mean and extremes mn, mx (zeros and negatives are the other part):
+//   lik = n1 log(1 - xal) + n2 log(xal) + sum dnorm(x2, mean(x2), sd, log = TRUE)
+// with xal = n2 / n clamped to [1e-5, 1 - 1e-5], sd = 1 when n2 < 2.  The
+// dnorm sum in closed form: 0 (n2 = 0), -log(2 pi) / 2 (n2 = 1), else
+// -n2 (log(var) / 2 + log(2 pi) / 2) - (n2 - 1) / 2 with var = m2 / (n2 - 1).
+// n2 >= 2 equal values (mn == mx bitwise): sd = 0 and R's dnorm(x, x, 0, log =
+// TRUE) is +Inf, so lik = +Inf.
+__device__ inline double bimod_lik(double n, double n2, double m2, double mn, double mx)
+{
+    const double half_log_2pi = 0.918938533204672741780329736406;
+    const double xal = fmin(fmax(n2 / n, 1e-5), 1.0 - 1e-5);
+    const double zi = (n - n2) * log1p(-xal) + n2 * log(xal);
+    if (n2 < 1.0) return zi;
+    if (n2 < 2.0) return zi - half_log_2pi;
+    if (__double_as_longlong(mn) == __double_as_longlong(mx)) return __longlong_as_double(0x7ff0000000000000ll);
+    const double var = m2 / (n2 - 1.0);
+    return zi + (-n2 * (0.5 * log(var) + half_log_2pi) - (n2 - 1.0) * 0.5);
+}
+
+// pchisq(x, df = 3, lower.tail = FALSE) = erfc(sqrt(x / 2)) + sqrt(2 x / pi) exp(-x / 2),
+// erfc(sqrt(x / 2)) = 2 pnorm(-sqrt(x)).  R's IEEE cases decided here: x <= 0
+// (-Inf included) gives 1, +Inf gives 0 (the closed form is Inf * 0 there), NaN
+// stays NaN.
+__device__ inline double bimod_pchisq3_upper(double x)
+{
+    if (x != x) return x;
+    if (x <= 0.0) return 1.0;
+    if (x == __longlong_as_double(0x7ff0000000000000ll)) return 0.0;
+    const double two_over_pi = 0.636619772367581343075535053490;
+    return 2 * scc_pnorm_small_tail(-sqrt(x)) + sqrt(two_over_pi * x) * exp(-0.5 * x);
+}
+
 // -------------------------------------------------------- per (pair, gene)
 __device__ inline u64 f_tie3(u64 c) { return c * c * c - c; }
 
@@ -300,7 +336,30 @@ __global__ void __launch_bounds__(256) k_pair_test(ScTestLaunch A)
         A.out_t[pg] = 0;
         return;
     }
-    const u64 pa = A.cnt_pos[(size_t)a * A.G + g], ga = A.cnt_neg[(size_t)a * A.G + g];
+    if (A.test == SCC_TEST_BIMOD) {  // DiffExpTest: lrt = 2 (lik(x) + lik(y) - lik(c(x, y))), df = 3
+        const size_t ia = (size_t)a * A.G + g, ib = (size_t)b * A.G + g;
+        const double pa = (double)A.cnt_pos[ia], pb = (double)A.cnt_pos[ib];
+        const double ma = A.mean_pos[ia], mb = A.mean_pos[ib];
+        const double la = bimod_lik((double)na, pa, A.m2_pos[ia], A.min_pos[ia], A.max_pos[ia]);
+        const double lb = bimod_lik((double)nb, pb, A.m2_pos[ib], A.min_pos[ib], A.max_pos[ib]);
+        // the pooled group: Chan's merge of the two parts' m2 (every term >= 0);
+        // a part without values > 0 has m2 = 0, min = +Inf, max = -Inf and drops
+        // out, so the pooled values are all equal exactly when both parts' are
+        // and share the value
+        double m2 = A.m2_pos[ia] + A.m2_pos[ib];
+        if (pa > 0.0 && pb > 0.0) m2 += (ma - mb) * (ma - mb) * (pa * pb / (pa + pb));
+        const double lc = bimod_lik((double)na + (double)nb, pa + pb, m2, fmin(A.min_pos[ia], A.min_pos[ib]),
+                                    fmax(A.max_pos[ia], A.max_pos[ib]));
+        const double pv = bimod_pchisq3_upper(2 * (la + lb - lc));  // Inf - Inf: NaN
+        // a NaN p of a tested cell becomes an NA p_val_adj, an all-NA marker row
+        // and an NA in deGeneUnion, where dataMatrix[deGeneUnion, ] stops
+        if (pv != pv && (fl & 1)) atomicOr(A.err, 0x20);
+        A.out_p[pg] = pv;
+        A.out_u2[pg] = 0;
+        A.out_t[pg] = 0;
+        return;
+    }
+    const u64 pa =A.cnt_pos[(size_t)a * A.G + g], ga = A.cnt_neg[(size_t)a * A.G + g];
     const u64 pb = A.cnt_pos[(size_t)b * A.G + g], gb = A.cnt_neg[(size_t)b * A.G + g];
     const u64 za = (u64)na - pa - ga, zb = (u64)nb - pb - gb;
     const u64 S = A.accS[pg] + za * gb + pa * zb;  // x > y, zeros included
