@@ -381,6 +381,22 @@ SCC_API int scc_diag_eig_last_path(void);
 /* s_memtime stamps of the last scc_diag_small_syev's phases [8] */
 SCC_API int scc_diag_small_syev_stamps(unsigned long long* out);
 
+/* ---- diagnostics (tests): the DE p-value device functions on host arrays --
+ * Not on the R path.  Evaluates, element by element, the same device function
+ * the (pair, gene) test kernel calls, so that tests can sweep its whole domain
+ * (cluster sizes, tails and branches no dataset reaches).  All pointers are
+ * host pointers of n elements; arrays a kind does not read may be NULL.
+ *   kind 0  wilcox.test p from u2 = i0 (twice the statistic), the tie term i1
+ *           and the sizes m, nn (>= 1); the exact distribution table is built
+ *           as a run builds it, at the largest size below 50 passed.  out holds
+ *           2n values: the p, then 1.0 / 0.0 for the exact / normal branch.
+ *   kind 1  Welch two-sided p from t = a and df = b (2 pt(-|t|, df))
+ *   kind 2  the normal tail beyond |z|, z = a (min of pnorm's two tails)
+ *   kind 3  pchisq(a, df = 3, lower.tail = FALSE) of the bimod test
+ * Synchronises the device; returns 0 on success. */
+SCC_API int scc_diag_pvalues(int kind, int n, const double* a, const double* b, const long long* i0,
+                             const long long* i1, const int* m, const int* nn, double* out);
+
 #ifdef __cplusplus
 }
 #endif

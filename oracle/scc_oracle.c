@@ -399,6 +399,8 @@ static double orc_pbeta2(double x, double y, double a, double b, int lower)
 /* R nmath/pt.c, lower_tail, non-log */
 double orc_pt(double x, double n, int lower_tail)
 {
+    if (isnan(x) || isnan(n)) return x + n;
+    if (isinf(x)) return ((x < 0) == (lower_tail != 0)) ? 0.0 : 1.0; /* pt.c: before any regime (Inf / Inf below) */
     if (n > 4e5) {
         const double val = 1.0 / (4.0 * n);
         return orc_pnorm(x * (1.0 - val) / sqrt(1.0 + x * x * 2.0 * val), lower_tail);

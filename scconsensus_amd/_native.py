@@ -47,7 +47,7 @@ EXPORTS = [
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
-    "scc_diag_small_syev_stamps",
+    "scc_diag_small_syev_stamps", "scc_diag_pvalues",
 ]
 
 
@@ -144,6 +144,7 @@ def load():
         "scc_diag_cholinv": (ctypes.c_int, [vp, i32, dbl, vp, vp]),
         "scc_diag_eig_last_path": (ctypes.c_int, []),
         "scc_diag_small_syev_stamps": (ctypes.c_int, [vp]),
+        "scc_diag_pvalues": (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -599,6 +600,29 @@ class Engine:
                 eng.set_stream(None)
                 return False
         return _On()
+
+
+# ---------------------------------------------------------------- diagnostics
+DIAG_WILCOX, DIAG_T, DIAG_PNORM, DIAG_PCHISQ3 = 0, 1, 2, 3
+
+
+def diag_pvalues(kind, a=None, b=None, u2=None, tie=None, m=None, n=None):
+    """scc_diag_pvalues: the DE p-value device functions on arrays (tests).
+    DIAG_WILCOX (u2, tie, m, n) returns (p, exact_used); DIAG_T (a = t, b = df),
+    DIAG_PNORM (a = z) and DIAG_PCHISQ3 (a = x) return p."""
+    def arr(v, dt):
+        return None if v is None else np.ascontiguousarray(v, dt)
+    a, b = arr(a, np.float64), arr(b, np.float64)
+    u2, tie, m, n = arr(u2, np.int64), arr(tie, np.int64), arr(m, np.int32), arr(n, np.int32)
+    used = (u2, tie, m, n) if kind == DIAG_WILCOX else (a, b) if kind == DIAG_T else (a,)
+    if any(v is None for v in used) or len({v.shape for v in used}) != 1 or used[0].ndim != 1:
+        raise ValueError("diag_pvalues: the kind's arguments must be 1-d arrays of one length")
+    cnt = len(used[0])
+    out = np.empty(2 * cnt if kind == DIAG_WILCOX else cnt)
+    rc = load().scc_diag_pvalues(int(kind), cnt, _ptr(a), _ptr(b), _ptr(u2), _ptr(tie), _ptr(m), _ptr(n), _ptr(out))
+    if rc != 0:
+        raise SccError(SCC_ERR_HIP if 0 <= kind <= 3 else SCC_ERR_INVALID, "scc_diag_pvalues failed")
+    return (out[:cnt], out[cnt:] != 0) if kind == DIAG_WILCOX else out
 
 
 # ---------------------------------------------------------------- host clustering

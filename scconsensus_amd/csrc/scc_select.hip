@@ -11,6 +11,9 @@
 //                   (Fast:391) / first-30 of sort(|logfc|) (slow:214-222),
 //                   and first-occurrence keys for the union.
 //  k_union          unique(Gene) in row order (Fast:392) / union() (slow:224).
+//  k_diag_pvalues   diagnostic (scc_diag_pvalues): the p-value device functions
+//                   of k_pair_test on arrays of arguments, for the tests.
+#include "scc.h"
 #include "scc_common.hpp"
 #include "scc_kernels.hpp"
 #include "scc_sort.hpp"
@@ -192,6 +195,8 @@ __device__ inline double t_pbeta2(double x, double y, double a, double b, bool l
 __device__ inline double t_two_sided(double t, double n)
 {
     const double x = -fabs(t);
+    if (t != t || n != n) return t + n;
+    if (x == -__longlong_as_double(0x7ff0000000000000ll)) return 0.0;  // pt.c: !R_FINITE(x) first (Inf / Inf below)
     if (n > 4e5) {
         const double val = 1.0 / (4.0 * n);
         return 2 * scc_pnorm_small_tail(x * (1.0 - val) / sqrt(1.0 + x * x * 2.0 * val));
@@ -929,4 +934,77 @@ extern "C" hipError_t scc_launch_flag_copy(const unsigned int* src, unsigned int
 {
     hipLaunchKernelGGL(k_flag_copy, dim3(1), dim3(1), 0, st, src, dst_dev);
     return hipGetLastError();
+}
+
+// -------------------------------------------------------- diagnostics
+// The p-value device functions k_pair_test calls, evaluated on arrays of
+// arguments (one thread per element): the tests sweep their whole domain
+// through this, which no dataset reaches.  kind 0 wilcox_p(u2 = i0, tie = i1,
+// nx = m, ny = nn) with out[n + e] = its exact_used flag, 1 t_two_sided(t = a,
+// df = b), 2 scc_pnorm_small_tail(z = a), 3 bimod_pchisq3_upper(x = a).
+__global__ void __launch_bounds__(256) k_diag_pvalues(int kind, int n, const double* a, const double* b,
+                                                      const long long* i0, const long long* i1, const int* m,
+                                                      const int* nn, const double* W, const int* woff, double* out)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    if (kind == 0) {
+        u8 ex = 0;
+        out[e] = wilcox_p((i64)i0[e], (i64)i1[e], m[e], nn[e], W, woff, &ex);
+        out[n + e] = (double)ex;
+    } else if (kind == 1) {
+        out[e] = t_two_sided(a[e], b[e]);
+    } else if (kind == 2) {
+        out[e] = scc_pnorm_small_tail(a[e]);
+    } else {
+        out[e] = bimod_pchisq3_upper(a[e]);
+    }
+}
+
+// Host pointers in and out.  kind 0 builds the cwilcox table as the runtime
+// does (ensure_wtab): scc_wilcox_table_layout, then k_wilcox_table at the
+// largest size below 50 among the arguments.  Returns 0 on success.
+extern "C" SCC_API int scc_diag_pvalues(int kind, int n, const double* a, const double* b, const long long* i0,
+                                        const long long* i1, const int* m, const int* nn, double* out)
+{
+    if (kind < 0 || kind > 3 || n < 0) return 1;
+    if (n == 0) return 0;
+    if (!out || (kind == 0 ? (!i0 || !i1 || !m || !nn) : (!a || (kind == 1 && !b)))) return 1;
+    if (kind == 0)
+        for (int e = 0; e < n; ++e)
+            if (m[e] < 1 || nn[e] < 1) return 1;
+    const size_t nout = (size_t)n * (kind == 0 ? 2 : 1);
+    void* dev[9] = {};
+    int rc = 1;
+    auto up = [&](int slot, const void* src, size_t bytes) {
+        return hipMalloc(&dev[slot], bytes) == hipSuccess &&
+               (!src || hipMemcpy(dev[slot], src, bytes, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    do {
+        if (kind == 0) {
+            int woff[WT_DIM * WT_DIM], mmax = 0;
+            const int total = scc_wilcox_table_layout(woff);
+            for (int e = 0; e < n; ++e) {
+                if (m[e] < WT_DIM && m[e] > mmax) mmax = m[e];
+                if (nn[e] < WT_DIM && nn[e] > mmax) mmax = nn[e];
+            }
+            if (!up(0, i0, sizeof(long long) * n) || !up(1, i1, sizeof(long long) * n) || !up(2, m, sizeof(int) * n) ||
+                !up(3, nn, sizeof(int) * n) || !up(4, nullptr, sizeof(double) * total) || !up(5, woff, sizeof(woff)))
+                break;
+            if (scc_launch_wilcox_table((double*)dev[4], (const int*)dev[5], mmax, nullptr) != hipSuccess) break;
+        } else {
+            if (!up(6, a, sizeof(double) * n) || (b && !up(7, b, sizeof(double) * n))) break;
+        }
+        if (!up(8, nullptr, sizeof(double) * nout)) break;
+        hipLaunchKernelGGL(k_diag_pvalues, dim3((n + 255) / 256), dim3(256), 0, nullptr, kind, n, (const double*)dev[6],
+                           (const double*)dev[7], (const long long*)dev[0], (const long long*)dev[1],
+                           (const int*)dev[2], (const int*)dev[3], (const double*)dev[4], (const int*)dev[5],
+                           (double*)dev[8]);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(out, dev[8], sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = 0;
+    } while (0);
+    for (void* d : dev)
+        if (d) (void)hipFree(d);
+    return rc;
 }
