@@ -153,7 +153,14 @@ SCC_API void scc_ctx_reset_timers(scc_ctx* ctx);
  * SCC_PTR_HOST copies the arrays; SCC_PTR_DEVICE borrows them, and their
  * contents must not change while the dataset lives: the first error-free DE
  * run that reads every entry marks the dataset validated (rows in range and
- * sorted) and caches nodg, and later gene-shard runs read only their genes. */
+ * sorted) and caches nodg, and later gene-shard runs read only their genes.
+ * The first FAST run after that (the dataset's second DE call) also builds a
+ * gene-major mirror of the kept entries on the device, 12 bytes per stored
+ * value, held until scc_dataset_destroy: later FAST runs regroup it by the
+ * call's clusters instead of transposing the matrix again (same results).
+ * It is built only while it needs at most a quarter of the free device
+ * memory; otherwise, and with SCC_INGEST_MIRROR=0, the per-call transpose
+ * stays. */
 SCC_API int scc_dataset_create_csc(scc_ctx* ctx, const int64_t* indptr, const int32_t* rows, const double* vals,
                            int64_t n_genes, int64_t n_cells, int64_t nnz, int32_t ptr_kind,
                            scc_dataset** out);
@@ -378,6 +385,12 @@ SCC_API int scc_diag_eigen_topk(const double* A, int n, int lda, int k, double* 
 SCC_API int scc_diag_small_syev(const double* H, int n, int ldh, int k, double* Y, double* theta, unsigned* flag);
 SCC_API int scc_diag_cholinv(const double* G, int P, double shift_rel, double* T, unsigned* flag);
 SCC_API int scc_diag_eig_last_path(void);
+/* Which ingest the calling thread's last DE run (scc_de_run, a gene shard, or
+ * the DE of scc_de_distance) took: 0 none yet, 1 the full read of the stored
+ * matrix (the validating first call, SLOW runs, dense datasets,
+ * SCC_INGEST_FULL=1), 2 the lean transpose of a validated dataset, 3 the
+ * regroup of the dataset's gene-major mirror. */
+SCC_API int scc_diag_ingest_last_path(void);
 /* s_memtime stamps of the last scc_diag_small_syev's phases [8] */
 SCC_API int scc_diag_small_syev_stamps(unsigned long long* out);
 

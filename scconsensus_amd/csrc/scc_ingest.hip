@@ -841,3 +841,335 @@ extern "C" hipError_t scc_launch_reduce_dd(const dd* parts, int n, dd* out, hipS
     hipLaunchKernelGGL(k_reduce_dd, dim3(1), dim3(64), 0, st, parts, n, out);
     return hipGetLastError();
 }
+
+// ===================================================== gene-major mirror
+// The transpose above depends on the matrix alone; only the grouping by
+// cluster depends on a call's labels.  A validated sparse dataset therefore
+// keeps a gene-major mirror of its kept (nonzero) entries,
+//     gptr[G + 1]   gene g's entries are [gptr[g], gptr[g + 1])
+//     cell[]        the entry's cell, ascending inside a gene
+//     key[]         its orderable value key (scc_key_of)
+// built once (k_mir_bcount, the column scan and scan above, k_mir_fill), and a
+// call's ingest is a stable partition of every gene's entries by the cells'
+// cluster codes (k_mir_regroup): read 12 B and write 8 B per entry in one
+// launch, instead of the count / column-scan / scan / scatter chain.  The host
+// orders kept cells by code and ascending cell index inside a code, so the
+// partition of a cell-ordered gene row lays the keys out as the scatter does.
+#define MR_T 256
+#define MR_CH 2048                 // entries staged per chunk (the key stage: 16 KB of LDS)
+#define MR_PER (MR_CH / MR_T)      // entries per lane and chunk; a wave owns 64 * MR_PER consecutive ones
+#define MR_BC 32                   // cells per build chunk (one wave; a count row each)
+
+// build, pass 1: cnt[chunk][g] = kept entries of gene g in the chunk's cells (cnt zeroed before)
+__global__ void __launch_bounds__(256) k_mir_bcount(const i64* __restrict__ indptr, const int* __restrict__ rows,
+                                                    const double* __restrict__ vals, int N, int G,
+                                                    u32* __restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const int ch = blockIdx.x * 4 + scc_wave_id();
+    const int c0 = ch * MR_BC, c1 = min(N, c0 + MR_BC);
+    if (c0 >= N) return;
+    const i64 b = indptr[c0], e = indptr[c1];
+    u32* row = cnt + (size_t)ch * G;
+    for (i64 k = b + lane; k < e; k += 64) {  // (rows are unique inside a cell: <= MR_BC adds per counter)
+        const int g = rows[k];
+        if (vals[k] != 0.0 && (unsigned)g < (unsigned)G) atomicAdd(&row[g], 1u);
+    }
+}
+
+// build, pass 2 (cnt: exclusive prefix over the chunks, per gene): a wave per
+// chunk walks its cells in ascending order, so the running count of (chunk,
+// gene) is the entry's rank among the gene's entries: ascending cells
+__global__ void __launch_bounds__(256) k_mir_fill(const i64* __restrict__ indptr, const int* __restrict__ rows,
+                                                  const double* __restrict__ vals, int N, int G,
+                                                  u32* __restrict__ cnt, const i64* __restrict__ gptr,
+                                                  u32* __restrict__ mcell, u64* __restrict__ mkey)
+{
+    const int lane = threadIdx.x & 63;
+    const int ch = blockIdx.x * 4 + scc_wave_id();
+    const int c0 = ch * MR_BC, c1 = min(N, c0 + MR_BC);
+    if (c0 >= N) return;
+    u32* row = cnt + (size_t)ch * G;
+    for (int c = c0; c < c1; ++c) {
+        const i64 b = indptr[c], e = indptr[c + 1];
+        for (i64 k = b + lane; k < e; k += 64) {
+            const int g = rows[k];
+            const double x = vals[k];
+            if (x != 0.0 && (unsigned)g < (unsigned)G) {
+                const i64 pos = gptr[g] + (i64)atomicAdd(&row[g], 1u);
+                if (pos < gptr[g + 1]) {  // always, for the validated matrix the counts were taken from
+                    mcell[pos] = (u32)c;
+                    mkey[pos] = scc_key_of(x);
+                }
+            }
+        }
+        // the next cell's counter updates after this cell's have returned
+        __threadfence_block();
+    }
+}
+
+// lanes of the wave (among those with act set) that hold the same code as this one (nb code bits)
+__device__ inline u64 mr_match(int a, bool act, int nb)
+{
+    u64 m = __ballot(act);
+    for (int b = 0; b < nb; ++b) {
+        const bool bit = (a >> b) & 1;
+        const u64 bb = __ballot(bit);
+        m &= bit ? bb : ~bb;
+    }
+    return m;
+}
+
+// wave 0: dst[a] = sum of src[0 .. a) for a in [0, SCC_MAX_K] (src[a] = 0 for a >= K), two clusters per lane
+__device__ inline void mr_scan_clusters(const u32* src, u32* dst, int K, int lane)
+{
+    const int a0 = 2 * lane;
+    const u32 v0 = a0 < K ? src[a0] : 0u, v1 = a0 + 1 < K ? src[a0 + 1] : 0u;
+    u32 inc = v0 + v1;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    dst[a0] = inc - v0 - v1;
+    dst[a0 + 1] = inc - v1;
+    if (lane == 63) dst[SCC_MAX_K] = inc;
+}
+
+// kept entries per gene (the labels' gstart when some cells are unkept, or for a gene shard)
+__global__ void __launch_bounds__(MR_T) k_mir_total(const i64* __restrict__ gptr, const u32* __restrict__ mcell,
+                                                    const signed char* __restrict__ code, int glo,
+                                                    u32* __restrict__ total)
+{
+    __shared__ u32 ws[MR_T / 64];
+    const int g = glo + blockIdx.x, lane = threadIdx.x & 63, wv = scc_wave_id();
+    const i64 b = gptr[g], e = gptr[g + 1];
+    u32 s = 0;
+    for (i64 k = b + threadIdx.x; k < e; k += MR_T) s += code[mcell[k]] >= 0;
+    s = u32_wave_sum(s);
+    if (lane == 0) ws[wv] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 t = 0;
+        for (int v = 0; v < MR_T / 64; ++v) t += ws[v];
+        total[g] = t;
+    }
+}
+
+// One workgroup per gene (longest genes first through `order`).  A chunk of
+// MR_CH entries at a time: every wave takes 64 * MR_PER consecutive entries,
+// 64 at a step; a ballot match on the code bits gives an entry's rank among
+// the step's entries of its cluster and the step's count per cluster (wc, no
+// dependent LDS chain), wave 0 turns the counts into each step's base inside
+// the chunk's per-cluster stretches, the keys are staged in LDS grouped by
+// cluster beside their destinations, and every stretch goes out as one
+// contiguous run at
+//     gstart[g] + coff[a] + (entries of cluster a in earlier chunks).
+// A gene longer than a chunk first counts its clusters (a pass over its
+// cells, 4 B per entry) for coff.  Writes rows cl_cc[0 .. K] of the offset
+// table cnt, the rows the stats, rank and split kernels read.
+#define MR_NS (MR_CH / 64)  // 64-entry steps of a chunk
+__global__ void __launch_bounds__(MR_T) k_mir_regroup(const i64* __restrict__ gptr, const u32* __restrict__ mcell,
+                                                      const u64* __restrict__ mkey,
+                                                      const signed char* __restrict__ code,
+                                                      const int* __restrict__ order, int glo, int K, int nb, int G,
+                                                      const int* __restrict__ cl_cc, const i64* __restrict__ gstart,
+                                                      u32* __restrict__ cnt, u64* __restrict__ keys)
+{
+    __shared__ u64 skey[MR_CH];
+    __shared__ u32 sdst[MR_CH];                 // a staged key's place in the gene's segment
+    // per step and cluster: the step's count, then its base inside the cluster's
+    // stretch (<= MR_CH: 16 bits; clusters 2 j and 2 j + 1 share a word)
+    __shared__ u32 wc[MR_NS][SCC_MAX_K / 2];
+    __shared__ u32 offs[2][SCC_MAX_K + 1];      // [0] the chunk's stretches in skey, [1] a long gene's cluster offsets
+    __shared__ u32 dbase[SCC_MAX_K];            // coff[a] + entries of cluster a in earlier chunks
+    __shared__ u32 tot[SCC_MAX_K];              // a long gene's counts
+    const int tid = threadIdx.x, lane = tid & 63, wv = scc_wave_id();
+    const int g = order ? order[blockIdx.x] : glo + blockIdx.x;
+    const i64 b = gptr[g];
+    const int n = (int)(gptr[g + 1] - b);
+    if (n <= 0) {
+        if (tid <= K) cnt[(size_t)cl_cc[tid] * G + g] = 0u;
+        return;
+    }
+    const i64 gs = gstart[g];
+    const bool multi = n > MR_CH;
+    const u64 below = (1ull << lane) - 1ull;
+    if (tid < SCC_MAX_K) tot[tid] = 0u;
+    __syncthreads();
+    if (multi) {
+        // (MR_PER loads in flight per lane: one at a time left the longest gene's
+        // count pass, a chain of dependent loads, as the kernel's tail)
+        for (int i0 = wv * (64 * MR_PER); i0 < n; i0 += MR_T * MR_PER) {
+            u32 cl[MR_PER];
+            int a[MR_PER];
+#pragma unroll
+            for (int u = 0; u < MR_PER; ++u) cl[u] = mcell[b + min(i0 + u * 64 + lane, n - 1)];
+#pragma unroll
+            for (int u = 0; u < MR_PER; ++u) a[u] = i0 + u * 64 + lane < n ? (int)code[cl[u]] : -1;
+#pragma unroll
+            for (int u = 0; u < MR_PER; ++u) {
+                const bool act = a[u] >= 0;
+                const u64 m = mr_match(a[u], act, nb);
+                if (act && (m & below) == 0ull) atomicAdd(&tot[a[u]], (u32)__popcll(m));
+            }
+        }
+        __syncthreads();
+        if (wv == 0) mr_scan_clusters(tot, offs[1], K, lane);
+    }
+    u32* const cst = offs[0];
+    const u32* const coff = offs[multi ? 1 : 0];  // (a gene of one chunk: the chunk's stretches)
+    // the chunk's cells and keys are loaded one chunk ahead (clamped
+    // unconditional loads, all in flight while the chunk before is regrouped)
+    u32 ncl[MR_PER];
+    u64 nkk[MR_PER];
+#pragma unroll
+    for (int u = 0; u < MR_PER; ++u) {
+        const int ic = min(wv * (64 * MR_PER) + u * 64 + lane, n - 1);
+        ncl[u] = mcell[b + ic];
+        nkk[u] = mkey[b + ic];
+    }
+    unsigned short* const wc16 = (unsigned short*)&wc[0][0];  // [MR_NS][SCC_MAX_K]
+    const int kw = (K + 1) >> 1;  // words of a wc row in use
+    u32 run0 = 0u, run1 = 0u;     // wave 0, lane j: entries of clusters 2 j and 2 j + 1 in earlier chunks
+    static_assert(MR_T / 8 == MR_NS && MR_T / 64 * MR_PER == MR_NS, "k_mir_regroup: a wc row per 8 threads");
+    for (int c0 = 0; c0 < n; c0 += MR_CH) {
+        const int len = min(MR_CH, n - c0);
+        for (int q = tid & 7; q < kw; q += 8) wc[tid >> 3][q] = 0u;  // (MR_T / 8 = MR_NS rows)
+        u64 kk[MR_PER];
+        int aa[MR_PER];
+        u32 rk[MR_PER];
+#pragma unroll
+        for (int u = 0; u < MR_PER; ++u) {
+            const int i = wv * (64 * MR_PER) + u * 64 + lane;
+            const int a = (int)code[ncl[u]];
+            kk[u] = nkk[u];
+            aa[u] = i < len ? a : -1;
+        }
+        if (c0 + MR_CH < n) {
+            const i64 nb0 = b + c0 + MR_CH;
+            const int nlen = n - c0 - MR_CH;  // (>= 1; entries past the gene's end are clamped to its last)
+#pragma unroll
+            for (int u = 0; u < MR_PER; ++u) {
+                const int ic = min(wv * (64 * MR_PER) + u * 64 + lane, nlen - 1);
+                ncl[u] = mcell[nb0 + ic];
+                nkk[u] = mkey[nb0 + ic];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < MR_PER; ++u) {  // step wv * MR_PER + u of the chunk
+            const bool act = aa[u] >= 0;
+            const u64 m = mr_match(aa[u], act, nb);
+            rk[u] = (u32)__popcll(m & below);
+            if (act && rk[u] == 0u)
+                wc16[(wv * MR_PER + u) * SCC_MAX_K + aa[u]] = (unsigned short)__popcll(m);
+        }
+        __syncthreads();
+        if (wv == 0) {
+            // lane j, clusters 2 j and 2 j + 1 (one word, no carry between the
+            // halves: a count is <= MR_CH): the steps' counts -> their bases
+            // inside the stretch, then the stretches by a scan over the lanes
+            u32 acc = 0u;
+            if (lane < kw) {
+                for (int s0 = 0; s0 < MR_NS; s0 += 8) {  // (8 reads in flight: all MR_NS cost registers)
+                    u32 x[8];
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) x[s] = wc[s0 + s][lane];
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) {
+                        wc[s0 + s][lane] = acc;
+                        acc += x[s];
+                    }
+                }
+            }
+            const u32 v0 = acc & 0xffffu, v1 = acc >> 16;
+            u32 inc = v0 + v1;
+            for (int o = 1; o < 64; o <<= 1) {
+                const u32 y = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += y;
+            }
+            const u32 e0 = inc - v0 - v1, e1 = inc - v1;  // the stretches' starts
+            cst[2 * lane] = e0;
+            cst[2 * lane + 1] = e1;
+            if (lane == 63) cst[SCC_MAX_K] = inc;
+            if (lane < kw) {  // (a gene of one chunk: coff is cst, still in registers)
+                dbase[2 * lane] = (multi ? coff[2 * lane] : e0) + run0;
+                dbase[2 * lane + 1] = (multi ? coff[2 * lane + 1] : e1) + run1;
+            }
+            run0 += v0;
+            run1 += v1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < MR_PER; ++u)
+            if (aa[u] >= 0) {
+                const u32 r = (u32)wc16[(wv * MR_PER + u) * SCC_MAX_K + aa[u]] + rk[u];  // rank inside the stretch
+                const u32 slot = cst[aa[u]] + r;
+                if (slot < (u32)MR_CH) {
+                    skey[slot] = kk[u];
+                    sdst[slot] = dbase[aa[u]] + r;
+                }
+            }
+        __syncthreads();
+        const int nk = (int)cst[K];
+        for (int i0 = tid; i0 < nk; i0 += 4 * MR_T) {  // stretches are contiguous in skey and in the segment
+            u64 kq[4];
+            u32 dq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = min(i0 + q * MR_T, nk - 1);
+                kq[q] = skey[i];
+                dq[q] = sdst[i];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (i0 + q * MR_T < nk) keys[gs + dq[q]] = kq[q];
+        }
+        if (c0 + MR_CH >= n) {  // the last chunk: the gene's rows of the offset table
+            if (tid <= K) cnt[(size_t)cl_cc[tid] * G + g] = coff[tid];
+        }
+        // (the next chunk's first barrier, before wave 0 rewrites cst, ends this chunk's reads)
+    }
+}
+
+extern "C" hipError_t scc_launch_mirror_build(const i64* indptr, const int* rows, const double* vals, i64 nnz, int N,
+                                              int G, u32* cnt, u32* colscan_scratch, i64* scan_scratch, i64* gptr,
+                                              u32* mcell, u64* mkey, hipStream_t st)
+{
+    const int nch = (N + MR_BC - 1) / MR_BC;
+    hipError_t e = hipMemsetAsync(cnt, 0, sizeof(u32) * (size_t)nch * G, st);
+    if (e != hipSuccess) return e;
+    // (every cell index the regroup reads is a valid one, whatever the fill wrote)
+    e = hipMemsetAsync(mcell, 0, sizeof(u32) * (size_t)std::max<i64>(1, nnz), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mir_bcount,dim3((nch + 3) / 4), dim3(256), 0, st, indptr, rows, vals, N, G, cnt);
+    e = scc_launch_ingest_colscan(cnt, nch, nch, G, 0, G, colscan_scratch, st);
+    if (e != hipSuccess) return e;
+    e = scc_launch_scan(cnt + (size_t)nch * G, G, gptr, scan_scratch, gptr + G, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mir_fill, dim3((nch + 3) / 4), dim3(256), 0, st, indptr, rows, vals, N, G, cnt, gptr, mcell,
+                       mkey);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t scc_launch_mirror_total(const i64* gptr, const u32* mcell, const signed char* code, int glo,
+                                              int ghi, u32* total, hipStream_t st)
+{
+    if (ghi <= glo) return hipSuccess;
+    hipLaunchKernelGGL(k_mir_total, dim3(ghi - glo), dim3(MR_T), 0, st, gptr, mcell, code, glo, total);
+    return hipGetLastError();
+}
+
+// order: genes by descending length (the whole range), or nullptr: genes [glo, ghi) in order
+extern "C" hipError_t scc_launch_mirror_regroup(const i64* gptr, const u32* mcell, const u64* mkey,
+                                                const signed char* code, const int* order, int glo, int ghi, int K,
+                                                int G, const int* cl_cc, const i64* gstart, u32* cnt, u64* keys,
+                                                hipStream_t st)
+{
+    if (ghi <= glo) return hipSuccess;
+    int nb = 0;
+    while ((1 << nb) < K) ++nb;
+    hipLaunchKernelGGL(k_mir_regroup, dim3(ghi - glo), dim3(MR_T), 0, st, gptr, mcell, mkey, code, order, glo, K, nb,
+                       G, cl_cc, gstart, cnt, keys);
+    return hipGetLastError();
+}

@@ -130,6 +130,15 @@ struct scc_dataset {
     // (clustering-independent), built by the first range-mode run: later
     // gene-shard runs read a cell's shard entries without binary searches
     mutable long long* d_tbnd = nullptr;
+    // the gene-major mirror of the kept (nonzero) entries, in ascending cell
+    // order inside each gene (clustering-independent; 12 B per stored value),
+    // built by the first FAST run on the validated dataset: every later FAST
+    // run's ingest regroups it by cluster instead of transposing the CSC
+    // (scc_ingest.hip).  m_order: the genes by descending length.
+    mutable long long* m_gptr = nullptr;          // [G + 1]
+    mutable unsigned int* m_cell = nullptr;       // [nnz]
+    mutable unsigned long long* m_key = nullptr;  // [nnz]
+    mutable int* m_order = nullptr;               // [G]
     // device list: the replica on each peer engine of the context (same order
     // as scc_ctx::peers), and the stored values per gene that balance the
     // gene row-blocks (computed on the first sharded run)

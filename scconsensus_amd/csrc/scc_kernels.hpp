@@ -205,6 +205,20 @@ hipError_t scc_launch_ingest_count_ro(const long long* indptr, const int* rows, 
 hipError_t scc_launch_scan(const uint32_t* in, long long n, long long* out, long long* bsum_scratch,
                            long long* total, hipStream_t st);
 int scc_scan_scratch_blocks(long long n);
+// the dataset's gene-major mirror (scc_ingest.hip): built once from the
+// validated CSC (cnt: ceil(N / 32) + 1 count rows of G; the
+// column scan's and the scan's scratch as for a run of that many chunks),
+// then regrouped by cluster at every call (code: int8 per cell, -1 unkept;
+// total: kept entries per gene of [glo, ghi) for the scan behind gstart)
+hipError_t scc_launch_mirror_build(const long long* indptr, const int* rows, const double* vals, long long nnz, int N,
+                                   int G, uint32_t* cnt, uint32_t* colscan_scratch, long long* scan_scratch,
+                                   long long* gptr, uint32_t* mcell, unsigned long long* mkey, hipStream_t st);
+hipError_t scc_launch_mirror_total(const long long* gptr, const uint32_t* mcell, const signed char* code, int glo,
+                                   int ghi, uint32_t* total, hipStream_t st);
+hipError_t scc_launch_mirror_regroup(const long long* gptr, const uint32_t* mcell, const unsigned long long* mkey,
+                                     const signed char* code, const int* order, int glo, int ghi, int K, int G,
+                                     const int* cl_cc, const long long* gstart, uint32_t* cnt,
+                                     unsigned long long* keys, hipStream_t st);
 // CSR -> CSC transpose (scc_csr.hip): a plan sized on the host from (G, N,
 // nnz), one scratch blob, a validating pass, then the two-pass transpose
 struct ScCsrPlan {

@@ -468,15 +468,34 @@ extern "C" int scc_dataset_read_csc(scc_dataset* d, int64_t* indptr, int32_t* ro
     return SCC_OK;
 }
 
+static void mirror_free(const scc_dataset* d)
+{
+    hipFree(d->m_gptr);
+    hipFree(d->m_cell);
+    hipFree(d->m_key);
+    hipFree(d->m_order);
+    d->m_gptr = nullptr;
+    d->m_cell = nullptr;
+    d->m_key = nullptr;
+    d->m_order = nullptr;
+}
+
+// which ingest the calling thread's last DE run took: 0 none yet, 1 the full
+// read (the validating call, SLOW, dense, SCC_INGEST_FULL), 2 the lean
+// transpose of a validated dataset, 3 the regroup of the dataset's mirror
+static thread_local int g_ingest_last_path = 0;
+extern "C" SCC_API int scc_diag_ingest_last_path(void) { return g_ingest_last_path; }
+
 extern "C" void scc_dataset_destroy(scc_dataset* d)
 {
     if (!d) return;
     for (scc_dataset* r : d->reps) scc_dataset_destroy(r);
     d->reps.clear();
-    if (d->owned || d->d_nodg || d->d_tbnd) {
+    if (d->owned || d->d_nodg || d->d_tbnd || d->m_gptr) {
         hipSetDevice(d->device);
         hipDeviceSynchronize();
     }
+    mirror_free(d);
     if (d->owned) {
         hipFree(d->d_indptr);
         hipFree(d->d_rows);
@@ -637,6 +656,13 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     H.insert(H.end(), cl_cc.begin(), cl_cc.end());
     const size_t o_nclu = H.size();
     H.insert(H.end(), nclu.begin(), nclu.end());
+    // the cells' codes as int8 (-1: unkept; K <= 128), for the mirror's regroup
+    const size_t o_code8 = H.size();
+    if (!finish_stage) {
+        H.resize(o_code8 + ((size_t)N + 3) / 4, 0);
+        signed char* c8 = (signed char*)(H.data() + o_code8);
+        for (int i = 0; i < N; ++i) c8[i] = (signed char)code[i];
+    }
 
     int rc;
     int *d_tab, *d_nodg, *d_splitg, *d_counts, *d_err, *d_tested, *d_union, *d_nu;
@@ -795,7 +821,89 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     const bool hist_ro = !hist_rng && !ds->dense && ds->validated && ds->no_zeros && ds->d_nodg && fast &&
                          !(ife && atoi(ife));
     hist_full = !hist_rng && !hist_ro;
-    {
+    // The dataset's gene-major mirror (FAST runs on a validated sparse dataset,
+    // whole range and gene shards alike): built here once, under its own timer,
+    // when it fits in a quarter of the free memory (the tile-start cache's
+    // rule; SCC_INGEST_MIRROR_MAX_BYTES lowers the limit, a test knob), else
+    // the transpose below stays.  SCC_INGEST_MIRROR=0 forces the transpose.
+    bool mirror = false;
+    if (!ds->dense && ds->validated && ds->d_nodg && fast && !(ife && atoi(ife)) &&
+        env_int("SCC_INGEST_MIRROR", 1) != 0) {
+        if (!ds->m_gptr) {
+            const size_t m_bytes = sizeof(long long) * ((size_t)G + 1) + sizeof(int) * (size_t)G +
+                                   (sizeof(unsigned int) + sizeof(unsigned long long)) * (size_t)nnz1;
+            size_t mfree = 0, mtot = 0;
+            bool room = hipMemGetInfo(&mfree, &mtot) == hipSuccess && m_bytes <= mfree / 4;
+            (void)hipGetLastError();
+            const char* mb = getenv("SCC_INGEST_MIRROR_MAX_BYTES");
+            if (mb && *mb && (double)m_bytes > atof(mb)) room = false;
+            if (room) {
+                if (hipMalloc((void**)&ds->m_gptr, sizeof(long long) * ((size_t)G + 1)) != hipSuccess ||
+                    hipMalloc((void**)&ds->m_order, sizeof(int) * (size_t)G) != hipSuccess ||
+                    hipMalloc((void**)&ds->m_cell, sizeof(unsigned int) * (size_t)nnz1) != hipSuccess ||
+                    hipMalloc((void**)&ds->m_key, sizeof(unsigned long long) * (size_t)nnz1) != hipSuccess) {
+                    (void)hipGetLastError();
+                    mirror_free(ds);
+                } else {
+                    uint32_t* d_cscr;
+                    WS("colscan", scc_ingest_colscan_scratch(nc, G), d_cscr);
+                    std::vector<long long> gp((size_t)G + 1);
+                    hipError_t e;
+                    {
+                        // (nc >= ceil(N / 32), the build's chunks: the run's count rows and scratch hold the build's)
+                        Scope sc(c, "ingest_mirror_build", s0);
+                        e = scc_launch_mirror_build(ds->d_indptr, ds->d_rows, ds->d_vals, nnz1, N, G, d_cnt, d_cscr,
+                                                    d_scan, ds->m_gptr, ds->m_cell, ds->m_key, s0);
+                        // the genes by descending length: the regroup's dispatch order
+                        if (e == hipSuccess)
+                            e = hipMemcpyAsync(gp.data(), ds->m_gptr, sizeof(long long) * gp.size(),
+                                               hipMemcpyDeviceToHost, s0);
+                        if (e == hipSuccess) e = hipStreamSynchronize(s0);
+                        if (e == hipSuccess) {
+                            std::vector<int> ord(G);
+                            for (int g = 0; g < G; ++g) ord[g] = g;
+                            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) {
+                                return gp[x + 1] - gp[x] > gp[y + 1] - gp[y];
+                            });
+                            e = hipMemcpy(ds->m_order, ord.data(), sizeof(int) * (size_t)G, hipMemcpyHostToDevice);
+                        }
+                    }
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        mirror_free(ds);
+                        return fail(c, SCC_ERR_HIP, std::string("mirror build failed: ") + hipGetErrorString(e));
+                    }
+                }
+            }
+        }
+        mirror = ds->m_gptr != nullptr;
+        if (mirror && ds->d_tbnd) {  // the transpose's tile starts: not needed any more
+            hipFree(ds->d_tbnd);
+            ds->d_tbnd = nullptr;
+        }
+    }
+    if (mirror) hist_rng = hist_full = false;
+    g_ingest_last_path = mirror ? 3 : hist_full ? 1 : 2;
+    long long* gstart_run = d_gstart;  // the genes' starts in d_keys (the mirror's own when every cell is kept)
+    if (mirror) {
+        Scope sc(c, "ingest", s0);
+        HIPCHK(c, scc_launch_de_clear(d_err, d_counts, norank ? nullptr : d_acc, (long long)acc_n, d_first, (int)G, glo,
+                                      ghi, s0));
+        de_cleared = true;
+        HIPCHK(c, hipMemcpyAsync(d_nodg, ds->d_nodg, sizeof(int) * N, hipMemcpyDeviceToDevice, s0));
+        const signed char* d_code8 = (const signed char*)(d_tab + o_code8);
+        const bool whole = glo == 0 && ghi == G;
+        if (whole && nkept == N) {
+            gstart_run = ds->m_gptr;
+        } else {
+            uint32_t* d_total = d_cnt + (size_t)nc * G;  // (the totals row of the transpose; zero outside a shard)
+            if (!whole) HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(uint32_t) * G, s0));
+            HIPCHK(c, scc_launch_mirror_total(ds->m_gptr, ds->m_cell, d_code8, glo, ghi, d_total, s0));
+            HIPCHK(c, scc_launch_scan(d_total, G, d_gstart, d_scan, d_gstart + G, s0));
+        }
+        HIPCHK(c, scc_launch_mirror_regroup(ds->m_gptr, ds->m_cell, ds->m_key, d_code8, whole ? ds->m_order : nullptr,
+                                            glo, ghi, K, G, d_clcc, gstart_run, d_cnt, d_keys, s0));
+    } else {
         Scope sc(c, "ingest", s0);
         // error words, counters, rank accumulators and first-occurrence keys in one launch
         HIPCHK(c, scc_launch_de_clear(d_err, d_counts, norank ? nullptr : d_acc, (long long)acc_n, d_first, (int)G, glo,
@@ -847,7 +955,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
     {
         Scope sc(c, "gene_stats", s0);
         ScStatsLaunch S{};
-        S.gstart = d_gstart;
+        S.gstart = gstart_run;
         S.keys = d_keys;
         S.G = G;
         S.K = K;
@@ -930,7 +1038,7 @@ static int de_run_body(scc_ctx* c, const scc_dataset* ds, const int32_t* code, i
         Scope sc(c, "gene_rank", s0);
         if (!de_cleared) HIPCHK(c, hipMemsetAsync(d_acc, 0, sizeof(unsigned long long) * acc_n, s0));
         ScRankLaunch L{};
-        L.gstart = d_gstart;
+        L.gstart = gstart_run;
         L.keys = d_keys;
         L.G = G;
         L.K = K;
