@@ -372,6 +372,30 @@ SCC_API int scc_hclust_ward_d2(const double* dist, int64_t n, int32_t* merge, do
 SCC_API int scc_cutree_hybrid(const int32_t* merge, const double* height, int64_t n, const double* dist,
                               int32_t deep_split, int32_t min_cluster_size, int32_t* labels, double* cut_height);
 
+/* ---- the same two on the device-resident distance -----------------------
+ * The tree and the cut without the packed vector ever crossing PCIe (opt-in;
+ * Fast:406-431, slow:242-266).  For the same distance values both return
+ * exactly what the host functions return (merge, height, order, labels and
+ * cut height bit for bit): the NN-chain runs in one workgroup with the host's
+ * scan order and update arithmetic (scc_hclust.hip), the tree cut reads its
+ * core x core blocks through a gather kernel and sums them on the host.
+ *
+ * fastcluster::hclust(d, "ward.D2") on a device-resident packed dist.  dist: device pointer
+ * (f64, or f32 if dist_f32), or NULL = the engine-kept output of the last full scc_distance
+ * call (as scc_silhouette).  merge/height/order: host, as scc_hclust_ward_d2.
+ * SCC_ERR_NONFINITE: a non-finite entry; SCC_ERR_INVALID: no kept distance, or one of another
+ * size; SCC_ERR_OOM: the full symmetric working copy (8 n^2 bytes, freed before returning)
+ * does not fit in half of the free device memory; SCC_ERR_HIP: the chain passed a loop cap.
+ * The chain runs as ceil((n - 1) / SCC_HCLUST_MERGES_PER_LAUNCH) launches (timer family
+ * "hclust_dev"; the expansion: "hclust_expand"). */
+#define SCC_HCLUST_MERGES_PER_LAUNCH 1024
+SCC_API int scc_hclust_ward_d2_dev(scc_ctx* ctx, int64_t n, const void* dist, int32_t dist_f32, int32_t* merge,
+                                   double* height, int32_t* order);
+/* scc_cutree_hybrid with distM read from the device-resident dist (same NULL rule). */
+SCC_API int scc_cutree_hybrid_dev(scc_ctx* ctx, const int32_t* merge, const double* height, int64_t n,
+                                  const void* dist, int32_t dist_f32, int32_t deep_split, int32_t min_cluster_size,
+                                  int32_t* labels, double* cut_height);
+
 /* ---- diagnostics (tests): the PCA eigensolver's parts on device pointers --
  * Not on the R path.  Each synchronises the device and returns 0 on success.
  *   scc_diag_eigen_topk   top-k eigenpairs of a device n x n symmetric A (lda)
@@ -391,6 +415,9 @@ SCC_API int scc_diag_eig_last_path(void);
  * SCC_INGEST_FULL=1), 2 the lean transpose of a validated dataset, 3 the
  * regroup of the dataset's gene-major mirror. */
 SCC_API int scc_diag_ingest_last_path(void);
+/* Nearest-neighbour scans (one row each) of the context's last
+ * scc_hclust_ward_d2_dev, for bandwidth figures; -1 without a context. */
+SCC_API int64_t scc_diag_hclust_last_scans(const scc_ctx* ctx);
 /* s_memtime stamps of the last scc_diag_small_syev's phases [8] */
 SCC_API int scc_diag_small_syev_stamps(unsigned long long* out);
 

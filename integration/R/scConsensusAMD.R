@@ -87,6 +87,31 @@
   list(tree = tree, colors = colors)
 }
 
+# options(scConsensus.engineTree = "device"): the distance stays in the engine's
+# HBM, hclust(ward.D2) (Fast:406-411, slow:242-247) and the hybrid cuts
+# (Fast:421-427, slow:257-263) run on it there; no "dist" object and no
+# as.matrix(d) on the host.  Same tree and labels as engineTree = TRUE with
+# engineCut = TRUE (the engine's restatements; parity against fastcluster /
+# dynamicTreeCut themselves unpinned: INTEGRATION.md)
+.scc_tree_on_device <- function() identical(getOption("scConsensus.engineTree", FALSE), "device")
+
+.scc_tree_and_colors_dev <- function(h, genes, n_cells, deepSplitValues, minClusterSize, with_si, metric = 0L) {
+  .Call("C_scc_distance_dev", h, as.integer(genes), as.integer(metric), 0L)
+  t <- .Call("C_scc_hclust_dev", as.integer(n_cells))
+  tree <- structure(list(merge = t[[1]], height = t[[2]], order = t[[3]], labels = NULL,
+                         method = "ward.D2", call = match.call(),
+                         dist.method = if (metric == 0L) "euclidean" else "pearson"),
+                    class = "hclust")
+  colors <- list()
+  for (dsv in deepSplitValues) {
+    grp <- .Call("C_scc_cutree_dev", tree$merge, as.double(tree$height), as.integer(dsv), as.integer(minClusterSize))
+    colors[[paste("deepsplit:", dsv)]] <- WGCNA::labels2colors(grp)
+    if (with_si) invisible(.Call("C_scc_si", as.integer(grp)))
+  }
+  names(colors) <- paste("deepsplit:", deepSplitValues)
+  list(tree = tree, colors = colors)
+}
+
 reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method = "wilcox",
                                      qValThrs = 0.1, logFCThrs = 0.5, deepSplitValues = 1:4,
                                      minClusterSize = 10, minPerCent = 20,
@@ -106,8 +131,12 @@ reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method 
                as.integer(NumbertopDEGenes), match(method, tests) - 1L)
   deGeneUnion <- rownames(dataMatrix)[res[[1]]]
   print(str(deGeneUnion))
-  d <- .scc_dist(h, res[[1]], ncol(dataMatrix))
-  tc <- .scc_tree_and_colors(d, deepSplitValues, minClusterSize, with_si = TRUE)
+  tc <- if (.scc_tree_on_device()) {
+    .scc_tree_and_colors_dev(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = TRUE)
+  } else {
+    d <- .scc_dist(h, res[[1]], ncol(dataMatrix))
+    .scc_tree_and_colors(d, deepSplitValues, minClusterSize, with_si = TRUE)
+  }
   out <- list("deGeneUnion" = deGeneUnion, "cellTree" = tc$tree, "dynamicColors" = tc$colors)
   saveRDS(object = out, file = filename)
   cellTypeDEPlot(dataMatrix = dataMatrix[deGeneUnion, ], nodg = res[[2]], cellTree = tc$tree,
@@ -147,8 +176,12 @@ reclusterDEConsensus <- function(dataMatrix, consensusClusterLabels, method = "W
   deGeneUnion <- rownames(dataMatrix)[res[[1]]]
   print(str(deGeneUnion))
   saveRDS(deGeneUnion, file = "deGeneUnion.rds")
-  d <- .scc_dist(h, res[[1]], ncol(dataMatrix))
-  tc <- .scc_tree_and_colors(d, deepSplitValues, minClusterSize, with_si = FALSE)
+  tc <- if (.scc_tree_on_device()) {
+    .scc_tree_and_colors_dev(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = FALSE)
+  } else {
+    d <- .scc_dist(h, res[[1]], ncol(dataMatrix))
+    .scc_tree_and_colors(d, deepSplitValues, minClusterSize, with_si = FALSE)
+  }
   out <- list("deGeneUnion" = deGeneUnion, "cellTree" = tc$tree, "dynamicColors" = tc$colors)
   saveRDS(object = out, file = filename)
   cellTypeDEPlot(dataMatrix = as.matrix(dataMatrix)[deGeneUnion, ], nodg = res[[5]], cellTree = tc$tree,

@@ -20,6 +20,11 @@
  *                   (options(scConsensus.engineCut = TRUE))
  *   C_scc_hclust    hclust(d, "ward.D2") (Fast:406-411) restated in C++
  *                   (options(scConsensus.engineTree = TRUE))
+ *   C_scc_distance_dev, C_scc_hclust_dev, C_scc_cutree_dev
+ *                   options(scConsensus.engineTree = "device"): the distance
+ *                   stays in the engine (Fast:398-400), the tree (Fast:406-411,
+ *                   slow:242-247) and the cuts (Fast:421-427, slow:257-263) are
+ *                   computed on it there; no "dist" object reaches R
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -315,6 +320,62 @@ SEXP C_scc_hclust(SEXP d)
     return out;
 }
 
+/* C_scc_distance with the output kept in the engine (HBM-resident, read by
+ * C_scc_hclust_dev / C_scc_cutree_dev / C_scc_si): returns the cell count */
+SEXP C_scc_distance_dev(SEXP h, SEXP genes, SEXP metric, SEXP ncomp)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes);
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int k = 0; k < nu; ++k) {
+        g0[k] = INTEGER(genes)[k] - 1;
+        if (g0[k] < 0 || g0[k] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[k] + 1);
+    }
+    check(scc_distance(g_ctx, ds, g0, nu, Rf_asInteger(metric), Rf_asInteger(ncomp), NULL, SCC_PTR_DEVICE, 0));
+    return Rf_ScalarInteger(N);
+}
+
+/* C_scc_hclust on the engine-kept distance of n cells (scc_hclust_ward_d2_dev:
+ * the same merge / height / order as C_scc_hclust on the same values) */
+SEXP C_scc_hclust_dev(SEXP n_cells)
+{
+    ensure_ctx();
+    const int64_t n = Rf_asInteger(n_cells);
+    if (n < 2) Rf_error("scConsensus engine: hclust needs at least two cells");
+    SEXP merge = PROTECT(Rf_allocMatrix(INTSXP, (int)(n - 1), 2));
+    SEXP height = PROTECT(Rf_allocVector(REALSXP, n - 1));
+    SEXP order = PROTECT(Rf_allocVector(INTSXP, n));
+    const int rc = scc_hclust_ward_d2_dev(g_ctx, n, NULL, 0, INTEGER(merge), REAL(height), INTEGER(order));
+    if (rc != SCC_OK) {
+        UNPROTECT(3);
+        check(rc);
+    }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, merge);
+    SET_VECTOR_ELT(out, 1, height);
+    SET_VECTOR_ELT(out, 2, order);
+    UNPROTECT(4);
+    return out;
+}
+
+/* C_scc_cutree with distM read from the engine-kept distance (scc_cutree_hybrid_dev) */
+SEXP C_scc_cutree_dev(SEXP merge, SEXP height, SEXP deep, SEXP minsize)
+{
+    ensure_ctx();
+    const int64_t n = (int64_t)XLENGTH(height) + 1;
+    if (XLENGTH(merge) != 2 * (n - 1))
+        Rf_error("scConsensus engine: merge / height do not match (%lld cells)", (long long)n);
+    SEXP m = PROTECT(Rf_coerceVector(merge, INTSXP));
+    SEXP lab = PROTECT(Rf_allocVector(INTSXP, n));
+    const int rc = scc_cutree_hybrid_dev(g_ctx, INTEGER(m), REAL(height), n, NULL, 0, Rf_asInteger(deep),
+                                         Rf_asInteger(minsize), INTEGER(lab), NULL);
+    UNPROTECT(2);
+    check(rc);
+    return lab;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"C_scc_dataset", (DL_FUNC)&C_scc_dataset, 4},
     {"C_scc_release", (DL_FUNC)&C_scc_release, 1},
@@ -325,6 +386,9 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_devices", (DL_FUNC)&C_scc_devices, 1},
     {"C_scc_cutree", (DL_FUNC)&C_scc_cutree, 5},
     {"C_scc_hclust", (DL_FUNC)&C_scc_hclust, 1},
+    {"C_scc_distance_dev", (DL_FUNC)&C_scc_distance_dev, 4},
+    {"C_scc_hclust_dev", (DL_FUNC)&C_scc_hclust_dev, 1},
+    {"C_scc_cutree_dev", (DL_FUNC)&C_scc_cutree_dev, 4},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

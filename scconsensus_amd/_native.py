@@ -33,6 +33,7 @@ SCC_DIST_PCA_EUCLID = 0
 SCC_DIST_PEARSON = 1
 SCC_PTR_HOST = 0
 SCC_PTR_DEVICE = 1
+HCLUST_MERGES_PER_LAUNCH = 1024  # SCC_HCLUST_MERGES_PER_LAUNCH: merges per chain launch of hclust_ward_d2_dev
 
 # every symbol include/scc.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -45,9 +46,9 @@ EXPORTS = [
     "scc_de_result_pair_vectors", "scc_de_result_log_threshold", "scc_de_result_nodg", "scc_de_result_destroy",
     "scc_distance", "scc_de_distance", "scc_distance_cols", "scc_pca_shard_colsum", "scc_pca_shard_gram", "scc_pca_shard_scores", "scc_pca_shard_eigen", "scc_pca_shard_project",
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
-    "scc_hclust_ward_d2", "scc_cutree_hybrid",
+    "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
-    "scc_diag_ingest_last_path",
+    "scc_diag_ingest_last_path", "scc_diag_hclust_last_scans",
     "scc_diag_small_syev_stamps", "scc_diag_pvalues",
 ]
 
@@ -140,6 +141,9 @@ def load():
         "scc_last_pca_scores": (ctypes.c_int, [vp, vp, P(i32)]),
         "scc_hclust_ward_d2": (ctypes.c_int, [vp, i64, vp, vp, vp]),
         "scc_cutree_hybrid": (ctypes.c_int, [vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
+        "scc_hclust_ward_d2_dev": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, vp]),
+        "scc_cutree_hybrid_dev": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, i32, vp, P(dbl)]),
+        "scc_diag_hclust_last_scans": (i64, [vp]),
         "scc_diag_eigen_topk": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, P(ctypes.c_int)]),
         "scc_diag_small_syev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp]),
         "scc_diag_cholinv": (ctypes.c_int, [vp, i32, dbl, vp, vp]),
@@ -562,6 +566,42 @@ class Engine:
         self._check(self.lib.scc_silhouette(self.ctx, N, _ptr(groups), ctypes.c_void_p(dist_device_ptr or None),
                                             1 if f32 else 0, _ptr(w), _ptr(ca), ctypes.byref(k)))
         return w, ca[:k.value]
+
+    def hclust_ward_d2_dev(self, N, dist_device_ptr=None, f32=False):
+        """hclust_ward_d2 on a device-resident packed distance (the engine-kept
+        output of the last full distance() call unless a device pointer is
+        given): the same (merge, height, order), bit for bit, and the packed
+        vector never leaves the device."""
+        N = int(N)
+        if N < 2:
+            raise ValueError("hclust_ward_d2_dev needs at least two observations")
+        merge = np.zeros(2 * (N - 1), np.int32)
+        height = np.zeros(N - 1)
+        order = np.zeros(N, np.int32)
+        self._check(self.lib.scc_hclust_ward_d2_dev(self.ctx, N, ctypes.c_void_p(dist_device_ptr or None),
+                                                    1 if f32 else 0, _ptr(merge), _ptr(height), _ptr(order)))
+        return merge.reshape(2, N - 1).T.copy(), height, order
+
+    def cutree_hybrid_dev(self, merge, height, deep_split, min_cluster_size, dist_device_ptr=None, f32=False):
+        """cutree_hybrid with distM read from a device-resident packed distance
+        (same rule as hclust_ward_d2_dev): (labels, cut height)."""
+        merge = np.asarray(merge)
+        n = merge.shape[0] + 1
+        m = np.ascontiguousarray(merge.T.reshape(-1), np.int32)
+        h = np.ascontiguousarray(height, np.float64)
+        if h.shape != (n - 1,):
+            raise ValueError("shape mismatch between merge and height")
+        lab = np.zeros(n, np.int32)
+        cut = ctypes.c_double()
+        self._check(self.lib.scc_cutree_hybrid_dev(self.ctx, _ptr(m), _ptr(h), n,
+                                                   ctypes.c_void_p(dist_device_ptr or None), 1 if f32 else 0,
+                                                   int(deep_split), int(min_cluster_size), _ptr(lab),
+                                                   ctypes.byref(cut)))
+        return lab, cut.value
+
+    def hclust_last_scans(self):
+        """Nearest-neighbour scans of the last hclust_ward_d2_dev (diagnostics)."""
+        return int(self.lib.scc_diag_hclust_last_scans(self.ctx))
 
     def last_pca_scores(self, N):
         k = ctypes.c_int32()

@@ -16,7 +16,10 @@ saved object stay on the host like in R; the pairwise DE, BH/filters/union and
 the distance matrix run in libscc on the GPU; hclust(ward.D2), cutreeDynamic
 (hybrid, pamStage = FALSE) and labels2colors run on the host as the reference
 keeps them there (libscc's host functions scc_hclust_ward_d2 /
-scc_cutree_hybrid).  The ComplexHeatmap plot is not part of
+scc_cutree_hybrid).  With ``tree="device"`` (opt-in) the
+distance stays in HBM and the tree and the cuts are computed on it there
+(scc_hclust_ward_d2_dev / scc_cutree_hybrid_dev: the same results bit for
+bit, no host copy of the distance).  The ComplexHeatmap plot is not part of
 this engine; ``plotName`` is ignored.
 """
 from __future__ import annotations
@@ -135,7 +138,19 @@ def _hclust_ward_d2(dist_packed, N):
     return {"merge": merge, "height": height, "order": order, "method": "ward.D2", "dist.method": "euclidean"}
 
 
-def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None, info=None):
+def _hclust_ward_d2_dev(eng, N):
+    """The same tree from the engine-kept distance (tree="device")."""
+    merge, height, order = eng.hclust_ward_d2_dev(N)
+    return {"merge": merge, "height": height, "order": order, "method": "ward.D2", "dist.method": "euclidean"}
+
+
+def _check_tree(tree):
+    if tree not in ("host", "device"):
+        raise ValueError(f"tree must be 'host' or 'device', not {tree!r}")
+    return tree == "device"
+
+
+def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None, info=None, cut_eng=None):
     """Fast:418-431: cutreeDynamic(dendro, distM = as.matrix(d), deepSplit = dsv,
     pamStage = FALSE, minClusterSize) -> labels2colors, named "deepsplit: dsv".
     With ``eng`` (FAST, which computes the silhouette for every deepSplit):
@@ -143,11 +158,16 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
     reference's deepSplitInfo rows
     (Fast:433: DeepSplit, NumbersOfClusters, SI = mean of
     summary(cluster::silhouette(groups, as.matrix(d)))$clus.avg.widths), the
-    silhouette computed by the engine on its HBM-resident copy of d."""
+    silhouette computed by the engine on its HBM-resident copy of d.
+    With ``cut_eng`` the cut reads that HBM-resident copy too (dist_packed is
+    not used)."""
     out = {}
     N = len(tree["order"])
     for dsv in deepSplitValues:
-        lab, _ = nat.cutree_hybrid(tree["merge"], tree["height"], dist_packed, int(dsv), int(minClusterSize))
+        if cut_eng is not None:
+            lab, _ = cut_eng.cutree_hybrid_dev(tree["merge"], tree["height"], int(dsv), int(minClusterSize))
+        else:
+            lab, _ = nat.cutree_hybrid(tree["merge"], tree["height"], dist_packed, int(dsv), int(minClusterSize))
         out[f"deepsplit: {dsv}"] = labels2colors(lab)
         if eng is not None:
             lab = np.asarray(lab, np.int32)
@@ -173,7 +193,9 @@ def _save(obj, filename):
 def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox", qValThrs=0.1, logFCThrs=0.5,
                              deepSplitValues=(1, 2, 3, 4), minClusterSize=10, minPerCent=20,
                              filename="de_gene_object.rds", plotName="DE_Heatmap", NumbertopDEGenes=30, nCores=1,
-                             *, gene_names=None, cluster_order=None, device=0, save=False, return_details=False):
+                             *, gene_names=None, cluster_order=None, device=0, save=False, return_details=False,
+                             tree="host"):
+    on_device = _check_tree(tree)
     if method not in ("wilcox", "t", "bimod"):
         # Fast:306-333: "roc" yields no p_val_adj, which the caller filters on (Fast:343-351,377)
         raise NotImplementedError(f"Unknown test: {method} (this engine implements test.use = 'wilcox', 't' "
@@ -197,11 +219,13 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
     print(f" chr [1:{len(uni)}] " + " ".join(f'"{g}"' for g in gnames[uni[:5]]) + (" ..." if len(uni) > 5 else ""))
     if len(uni) == 0:
         raise RuntimeError("no DE genes (R fails on an empty deGenes data frame, Fast:386)")
-    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID)
-    tree = _hclust_ward_d2(d, N)
+    # tree="device": the distance stays in the engine (d is None), the tree, the cuts and the silhouette read it there
+    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID, device_out_ptr=0 if on_device else None)
+    cell_tree = _hclust_ward_d2_dev(eng, N) if on_device else _hclust_ward_d2(d, N)
     info = [] if return_details else None  # deepSplitInfo: computed by the reference, never returned (Fast:433)
-    ret = {"deGeneUnion": list(gnames[uni]), "cellTree": tree,
-           "dynamicColors": _dynamic_colors(tree, d, deepSplitValues, minClusterSize, eng, info)}
+    ret = {"deGeneUnion": list(gnames[uni]), "cellTree": cell_tree,
+           "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize, eng, info,
+                                            cut_eng=eng if on_device else None)}
     if save:
         _save(ret, filename)
     if return_details:
@@ -214,7 +238,8 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
 def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", meanScalingFactor=5, qValThrs=None,
                          fcThrs=None, deepSplitValues=(1, 2, 3, 4), minClusterSize=10, filename="de_gene_object.rds",
                          plotName="DE_Heatmap", *, gene_names=None, cluster_order=None, device=0, save=False,
-                         return_details=False):
+                         return_details=False, tree="host"):
+    on_device = _check_tree(tree)
     if qValThrs is None or fcThrs is None:
         raise TypeError('argument "qValThrs"/"fcThrs" is missing, with no default')
     if method == "edgeR":
@@ -249,10 +274,11 @@ def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", 
     uni = res.union
     if len(uni) == 0:
         raise RuntimeError("empty DE gene union")
-    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID)
-    tree = _hclust_ward_d2(d, N)
-    ret = {"deGeneUnion": list(gnames[uni]), "cellTree": tree,
-           "dynamicColors": _dynamic_colors(tree, d, deepSplitValues, minClusterSize)}
+    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID, device_out_ptr=0 if on_device else None)
+    cell_tree = _hclust_ward_d2_dev(eng, N) if on_device else _hclust_ward_d2(d, N)
+    ret = {"deGeneUnion": list(gnames[uni]), "cellTree": cell_tree,
+           "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize,
+                                            cut_eng=eng if on_device else None)}
     if save:
         _save({"qValueList": qlist, "logFCList": lflist, "deGeneList": delist}, "de_lists")
         _save(ret, filename)

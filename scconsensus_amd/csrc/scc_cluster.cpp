@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "scc.h"
+#include "scc_cluster.hpp"
 
 namespace {
 
@@ -160,6 +161,8 @@ static void nn_chain_ward(WorkD<FULL>& D, std::vector<Step>& out)
     }
 }
 
+static void ward_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order);
+
 static void ward_d2(const double* dist, int64_t N, int32_t* merge, double* height, int32_t* order, bool full)
 {
     std::vector<Step> st;
@@ -178,6 +181,13 @@ static void ward_d2(const double* dist, int64_t N, int32_t* merge, double* heigh
         for (int64_t k = 0; k < M; ++k) D.d[(size_t)k] = dist[k] * dist[k];
         nn_chain_ward(D, st);
     }
+    ward_finish(st, N, merge, height, order);
+}
+
+// The chain's steps (h: squared merge distances) -> R's hclust fields; shared
+// with the device-resident chain (scc_cl::hclust_finish).
+static void ward_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order)
+{
     for (auto& s : st) s.h = std::sqrt(s.h);
     std::stable_sort(st.begin(), st.end(), [](const Step& x, const Step& y) { return x.h < y.h; });
     // union-find: the k-th merge in height order becomes node N + k
@@ -242,18 +252,24 @@ static double r_mean(const std::vector<double>& x)
     return (double)s;
 }
 
+struct FetchError {
+    int rc;
+};
+
 // mean(colSums(distM[Core, Core]) / (coresize - 1)); colSums accumulates in
-// long double (R's do_colsum); core holds 1-based object ids
-static double core_scatter(const double* dist, int64_t N, const int32_t* core, int cs)
+// long double (R's do_colsum); core holds 1-based object ids.  The core x
+// core block comes through `fetch` (the packed host vector, or a gather from
+// the device-resident one): the same values summed in the same order.
+static double core_scatter(const scc_cl::CoreFetch& fetch, std::vector<double>& block, const int32_t* core, int cs)
 {
+    block.resize((size_t)cs * (size_t)cs);
+    const int rc = fetch(core, cs, block.data());
+    if (rc != SCC_OK) throw FetchError{rc};
     std::vector<double> col((size_t)cs);
     for (int j = 0; j < cs; ++j) {
         long double s = 0.0L;
-        const int64_t cj = core[j] - 1;
-        for (int i = 0; i < cs; ++i) {
-            const int64_t ci = core[i] - 1;
-            s += ci == cj ? 0.0 : dist[pidx(N, ci, cj)];
-        }
+        const double* bj = &block[(size_t)j * (size_t)cs];
+        for (int i = 0; i < cs; ++i) s += bj[i];
         col[(size_t)j] = (double)s / (double)(cs - 1);
     }
     return r_mean(col);
@@ -278,15 +294,15 @@ static double interpolate(const double* data, int n, double index)
 }
 
 struct Branch {
-    bool is_basic = true, is_top_basic = true, fail_size = false;
+    bool is_basic = true, is_top_basic = true;
     double attach_height = NAN;
     int size = 2, n_merge = 1, n_basic = 0;
     int merged_into = 0;
     std::vector<int32_t> singletons, basic, merging_h_dummy;
 };
 
-static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, const double* dist, int deep_split,
-                         int min_cluster_size, int32_t* labels, double* cut_out, std::string& err)
+static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, const scc_cl::CoreFetch& fetch,
+                         int deep_split, int min_cluster_size, int32_t* labels, double* cut_out, std::string& err)
 {
     const int64_t n_merge = N - 1;
     double hmax = -INFINITY;
@@ -319,9 +335,10 @@ static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, 
     std::vector<Branch> br(1);  // 1-based like R
     br.reserve((size_t)n_below + 2);
     std::vector<int32_t> merge_to_branch((size_t)n_merge, 0);
+    std::vector<double> block;
     auto scatter_of = [&](const Branch& b) {
         const int cs = core_size((int)b.singletons.size(), min_cluster_size);
-        return core_scatter(dist, N, b.singletons.data(), cs);
+        return core_scatter(fetch, block, b.singletons.data(), cs);
     };
     for (int64_t m = 0; m < n_merge; ++m) {
         if (!(height[m] <= cut_height)) continue;
@@ -349,31 +366,29 @@ static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, 
             // rank(sizes, ties.method = "first"): the first is small unless strictly larger
             int32_t small = c1, large = c2;
             if (br[(size_t)c1].size > br[(size_t)c2].size) std::swap(small, large);
-            const double sm_ave = br[(size_t)small].is_basic ? scatter_of(br[(size_t)small]) : 0.0;
-            const double lg_ave = br[(size_t)large].is_basic ? scatter_of(br[(size_t)large]) : 0.0;
-            bool do_merge = false, smaller_fail_size = false;
-            {
-                const Branch& s = br[(size_t)small];
-                const bool c2s = s.size < min_cluster_size, c3 = sm_ave > max_abs_core_scatter,
-                           c4 = h - sm_ave < min_abs_gap, c5 = h < min_abs_split_height;
-                if (s.is_basic && (c2s || c3 || c4 || c5)) {
-                    do_merge = true;
-                    smaller_fail_size = !(c3 || c4);
-                } else {
-                    const Branch& l = br[(size_t)large];
-                    const bool d2 = l.size < min_cluster_size, d3 = lg_ave > max_abs_core_scatter,
-                               d4 = h - lg_ave < min_abs_gap, d5 = h < min_abs_split_height;
-                    if (l.is_basic && (d2 || d3 || d4 || d5)) {
-                        do_merge = true;
-                        smaller_fail_size = !(d3 || d4);
-                        std::swap(small, large);
-                    }
-                }
+            // A basic branch is merged away when it is too small, attaches
+            // below the split height, is too scattered or has too small a
+            // gap.  The core scatter (a read of the core x core distances) is
+            // taken only where the size and height criteria have not decided
+            // already: the merge decision is the same, and the package's
+            // failSize flag, the one other use of the scatter here, feeds the
+            // PAM stage only (pamStage = FALSE).
+            auto fails = [&](const Branch& b) {
+                if (!b.is_basic) return false;
+                if (b.size < min_cluster_size || h < min_abs_split_height) return true;
+                const double ave = scatter_of(b);
+                return ave > max_abs_core_scatter || h - ave < min_abs_gap;
+            };
+            bool do_merge = false;
+            if (fails(br[(size_t)small])) {
+                do_merge = true;
+            } else if (fails(br[(size_t)large])) {
+                do_merge = true;
+                std::swap(small, large);
             }
             if (do_merge) {
                 Branch& s = br[(size_t)small];
                 Branch& l = br[(size_t)large];
-                s.fail_size = smaller_fail_size;
                 s.merged_into = large;
                 s.attach_height = h;
                 s.is_top_basic = false;
@@ -429,9 +444,9 @@ static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, 
     for (int c = 1; c <= nb; ++c) {
         Branch& b = br[(size_t)c];
         if (std::isnan(b.attach_height)) b.attach_height = cut_height;
-        if (!b.is_top_basic) continue;
+        if (!b.is_top_basic || b.size < min_cluster_size) continue;
         const double cs = scatter_of(b);
-        if (b.size >= min_cluster_size && cs < max_abs_core_scatter && b.attach_height - cs > min_abs_gap) {
+        if (cs < max_abs_core_scatter && b.attach_height - cs > min_abs_gap) {
             ++color;
             for (int32_t g : b.singletons) colors[(size_t)g - 1] = color;
         }
@@ -450,6 +465,28 @@ static int cutree_hybrid(const int32_t* merge, const double* height, int64_t N, 
 }
 
 }  // namespace
+
+namespace scc_cl {
+
+void hclust_finish(int64_t n, const int32_t* a, const int32_t* b, const double* h2, int32_t* merge, double* height,
+                   int32_t* order)
+{
+    std::vector<Step> st((size_t)(n - 1));
+    for (int64_t k = 0; k < n - 1; ++k) st[(size_t)k] = Step{a[k], b[k], h2[k]};
+    ward_finish(st, n, merge, height, order);
+}
+
+int cutree_hybrid(const int32_t* merge, const double* height, int64_t n, const CoreFetch& fetch, int deep_split,
+                  int min_cluster_size, int32_t* labels, double* cut_out, std::string& err)
+{
+    try {
+        return ::cutree_hybrid(merge, height, n, fetch, deep_split, min_cluster_size, labels, cut_out, err);
+    } catch (const FetchError& e) {
+        return e.rc;
+    }
+}
+
+}  // namespace scc_cl
 
 extern "C" {
 
@@ -474,8 +511,19 @@ SCC_API int scc_cutree_hybrid(const int32_t* merge, const double* height, int64_
 {
     if (!merge || !height || !dist || !labels || n < 2) return SCC_ERR_INVALID;
     std::string err;
+    // distM[core, core] read from the packed host vector
+    const scc_cl::CoreFetch fetch = [dist, n](const int32_t* core, int cs, double* block) {
+        for (int j = 0; j < cs; ++j) {
+            const int64_t cj = core[j] - 1;
+            for (int i = 0; i < cs; ++i) {
+                const int64_t ci = core[i] - 1;
+                block[(size_t)j * (size_t)cs + (size_t)i] = ci == cj ? 0.0 : dist[pidx(n, ci, cj)];
+            }
+        }
+        return (int)SCC_OK;
+    };
     try {
-        return cutree_hybrid(merge, height, n, dist, deep_split, min_cluster_size, labels, cut_height, err);
+        return scc_cl::cutree_hybrid(merge, height, n, fetch, deep_split, min_cluster_size, labels, cut_height, err);
     } catch (const std::bad_alloc&) {
         return SCC_ERR_OOM;
     }

@@ -10,9 +10,11 @@
 // Pearson path (reference Fast:403, commented out there): per-cell z-scores
 // over U and an FP32 MFMA Gram with the 1 - r epilogue fused into the store.
 #include "scc_internal.hpp"
+#include "scc_cluster.hpp"
 
 #include <chrono>
 #include <functional>
+#include <new>
 #include <thread>
 
 using namespace scc_rt;
@@ -764,6 +766,29 @@ extern "C" int scc_distance_scores(scc_ctx* c, const void* scores, int64_t N64, 
     return SCC_OK;
 }
 
+// What a NULL `dist` stands for (scc_silhouette, scc_hclust_ward_d2_dev,
+// scc_cutree_hybrid_dev): the engine-kept output of the last full scc_distance
+// call, whole on this context's device (peer slices of a device-list distance
+// are copied in on first use).
+static int kept_dist(scc_ctx* c, int64_t N, const char* who, const void** D, int* f32)
+{
+    if (!c->d_last_dist || c->last_dist_n != N)
+        return fail(c, SCC_ERR_INVALID, std::string(who) + ": no full scc_distance output of this size is kept");
+    *D = c->d_last_dist;
+    *f32 = c->last_dist_f32;
+    const size_t es = *f32 ? 4 : 8;
+    hipSetDevice(c->device);
+    for (const auto& sl : c->last_dist_pending) {  // peer slices of a device-list distance
+        char* dst = (char*)c->d_last_dist + sl.off * es;
+        if (sl.dev == c->device)
+            HIPCHK(c, hipMemcpyAsync(dst, sl.ptr, sl.n * es, hipMemcpyDeviceToDevice, c->s0));
+        else
+            HIPCHK(c, hipMemcpyPeerAsync(dst, c->device, sl.ptr, sl.dev, sl.n * es, c->s0));
+    }
+    c->last_dist_pending.clear();
+    return SCC_OK;
+}
+
 extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups, const void* dist, int32_t dist_f32,
                               double* widths, double* clus_avg, int32_t* n_groups)
 {
@@ -773,20 +798,8 @@ extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups
     const void* D = dist;
     int f32 = dist_f32 ? 1 : 0;
     if (!D) {
-        if (!c->d_last_dist || c->last_dist_n != N)
-            return fail(c, SCC_ERR_INVALID, "scc_silhouette: no full scc_distance output of this size is kept");
-        D = c->d_last_dist;
-        f32 = c->last_dist_f32;
-        const size_t es = f32 ? 4 : 8;
-        hipSetDevice(c->device);
-        for (const auto& sl : c->last_dist_pending) {  // peer slices of a device-list distance
-            char* dst = (char*)c->d_last_dist + sl.off * es;
-            if (sl.dev == c->device)
-                HIPCHK(c, hipMemcpyAsync(dst, sl.ptr, sl.n * es, hipMemcpyDeviceToDevice, c->s0));
-            else
-                HIPCHK(c, hipMemcpyPeerAsync(dst, c->device, sl.ptr, sl.dev, sl.n * es, c->s0));
-        }
-        c->last_dist_pending.clear();
+        int rck = kept_dist(c, N, "scc_silhouette", &D, &f32);
+        if (rck) return rck;
     }
     // cluster codes in increasing id order (silhouette's sorted clusters)
     std::vector<int32_t> ids(groups, groups + N);
@@ -831,6 +844,173 @@ extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups
         for (int k = 0; k < C; ++k) clus_avg[k] = (double)(sum[k] / cnt[k]);
     }
     return SCC_OK;
+}
+
+// ---- hclust(ward.D2) and the tree cut on the device-resident distance ------
+// (kernels and algorithm: scc_hclust.hip; post-processing and the cut itself:
+// scc_cluster.cpp, shared with the host entry points)
+
+namespace {
+
+struct DevFree {  // the working copy lives for one call
+    void* p = nullptr;
+    ~DevFree()
+    {
+        if (p) hipFree(p);
+    }
+};
+
+}  // namespace
+
+extern "C" int scc_hclust_ward_d2_dev(scc_ctx* c, int64_t n, const void* dist, int32_t dist_f32, int32_t* merge,
+                                      double* height, int32_t* order)
+{
+    if (!c || !merge || !height) return fail(c, SCC_ERR_INVALID, "scc_hclust_ward_d2_dev: null argument");
+    if (n < 2 || n > (int64_t)INT32_MAX) return fail(c, SCC_ERR_INVALID, "scc_hclust_ward_d2_dev: bad cell count");
+    const int N = (int)n;
+    scc_enter(c);
+    hipStream_t s0 = c->s0;
+    const void* P = dist;
+    int f32 = dist_f32 ? 1 : 0;
+    int rc;
+    if (!P && (rc = kept_dist(c, N, "scc_hclust_ward_d2_dev", &P, &f32))) return rc;
+    // the full symmetric working copy (the host's FULL layout), only when it
+    // fits in half of the free device memory
+    const size_t full_bytes = (size_t)N * (size_t)N * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    if (full_bytes > free_b / 2)
+        return fail(c, SCC_ERR_OOM,
+                    "scc_hclust_ward_d2_dev: the " + std::to_string(full_bytes >> 20) + " MiB working copy exceeds half of the " +
+                        std::to_string(free_b >> 20) + " MiB of free device memory");
+    DevFree full;
+    if (hipMalloc(&full.p, full_bytes) != hipSuccess) {
+        hipGetLastError();
+        full.p = nullptr;
+        return fail(c, SCC_ERR_OOM, "scc_hclust_ward_d2_dev: hipMalloc failed for the working copy");
+    }
+    double* d_full = (double*)full.p;
+    scc_hc_state* d_state;
+    unsigned int* d_bad;
+    int *d_chain, *d_a, *d_b;
+    double *d_size, *d_h;
+    uint8_t* d_act;
+    if ((rc = ws(c, "hc_state", 1, &d_state))) return rc;
+    if ((rc = ws(c, "hc_bad", 1, &d_bad))) return rc;
+    if ((rc = ws(c, "hc_chain", (size_t)N, &d_chain))) return rc;
+    if ((rc = ws(c, "hc_a", (size_t)N, &d_a))) return rc;
+    if ((rc = ws(c, "hc_b", (size_t)N, &d_b))) return rc;
+    if ((rc = ws(c, "hc_size", (size_t)N, &d_size))) return rc;
+    if ((rc = ws(c, "hc_h", (size_t)N, &d_h))) return rc;
+    if ((rc = ws(c, "hc_act", (size_t)N, &d_act))) return rc;
+    HIPCHK(c, scc_launch_hc_init(N, d_state, d_size, d_act, d_bad, s0));
+    {
+        Scope sc(c, "hclust_expand", s0);
+        HIPCHK(c, scc_launch_hc_expand(P, f32, N, d_full, d_bad, s0));
+    }
+    // the chain is never launched on a matrix with a non-finite entry (a NaN
+    // compares false both ways: fastcluster's nan_error)
+    unsigned int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    if (!dist && (rc = check_pending_eig(c))) {
+        c->d_last_dist = nullptr;
+        return rc;
+    }
+    if (bad) return fail(c, SCC_ERR_NONFINITE, "scc_hclust_ward_d2_dev: the distance holds a non-finite entry");
+    // ceil((n - 1) / M) bounded launches, queued back to back
+    const int M = SCC_HCLUST_MERGES_PER_LAUNCH;
+    for (int done = 0; done < N - 1; done += M) {
+        Scope sc(c, "hclust_dev", s0);
+        HIPCHK(c, scc_launch_hc_chain(d_full, N, d_state, d_chain, d_size, d_act, d_a, d_b, d_h, M, s0));
+    }
+    scc_hc_state st{};
+    std::vector<int32_t> a((size_t)N - 1), b((size_t)N - 1);
+    std::vector<double> h2((size_t)N - 1);
+    HIPCHK(c, hipMemcpyAsync(&st, d_state, sizeof(st), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipMemcpyAsync(a.data(), d_a, sizeof(int32_t) * a.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipMemcpyAsync(b.data(), d_b, sizeof(int32_t) * b.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipMemcpyAsync(h2.data(), d_h, sizeof(double) * h2.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    c->hc_last_scans = st.scans;
+    if (st.err == SCC_HC_ERR_CAP)
+        return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_dev: the NN-chain passed its scan cap at merge " +
+                                        std::to_string(st.step) + " (corrupt working matrix?)");
+    if (st.err || st.step != N - 1)
+        return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_dev: the NN-chain stopped at merge " + std::to_string(st.step) +
+                                        " with an index out of range");
+    for (size_t k = 0; k < a.size(); ++k)
+        if (a[k] < 0 || a[k] >= N || b[k] < 0 || b[k] >= N)
+            return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_dev: a merge holds a node out of range");
+    try {
+        scc_cl::hclust_finish(N, a.data(), b.data(), h2.data(), merge, height, order);
+    } catch (const std::bad_alloc&) {
+        return fail(c, SCC_ERR_OOM, "scc_hclust_ward_d2_dev: host allocation failed");
+    }
+    return SCC_OK;
+}
+
+extern "C" int64_t scc_diag_hclust_last_scans(const scc_ctx* c) { return c ? (int64_t)c->hc_last_scans : -1; }
+
+extern "C" int scc_cutree_hybrid_dev(scc_ctx* c, const int32_t* merge, const double* height, int64_t n,
+                                     const void* dist, int32_t dist_f32, int32_t deep_split, int32_t min_cluster_size,
+                                     int32_t* labels, double* cut_height)
+{
+    if (!c || !merge || !height || !labels) return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_dev: null argument");
+    if (n < 2 || n > (int64_t)INT32_MAX) return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_dev: bad cell count");
+    const int N = (int)n;
+    scc_enter(c);
+    hipStream_t s0 = c->s0;
+    const void* P = dist;
+    int f32 = dist_f32 ? 1 : 0;
+    int rc;
+    if (!P) {
+        if ((rc = kept_dist(c, N, "scc_cutree_hybrid_dev", &P, &f32))) return rc;
+        HIPCHK(c, hipStreamSynchronize(s0));
+        if ((rc = check_pending_eig(c))) {
+            c->d_last_dist = nullptr;
+            return rc;
+        }
+    }
+    // distM[core, core]: the ids go up through the pinned buffer, the gather
+    // kernel writes the block straight back into it (tens of KB a fetch)
+    const scc_cl::CoreFetch fetch = [&](const int32_t* core, int cs, double* block) -> int {
+        for (int i = 0; i < cs; ++i)
+            if (core[i] < 1 || core[i] > N) return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_dev: object id out of range");
+        const size_t id_bytes = ((size_t)cs * sizeof(int) + 255) & ~(size_t)255;
+        const size_t blk_bytes = (size_t)cs * (size_t)cs * sizeof(double);
+        if (c->core_bytes < id_bytes + blk_bytes) {
+            if (c->h_core) hipHostFree(c->h_core);
+            c->h_core = nullptr;
+            c->core_bytes = 0;
+            const size_t want = std::max<size_t>((size_t)1 << 20, 2 * (id_bytes + blk_bytes));
+            if (hipHostMalloc((void**)&c->h_core, want, hipHostMallocMapped) != hipSuccess) {
+                hipGetLastError();
+                c->h_core = nullptr;
+                return fail(c, SCC_ERR_OOM, "scc_cutree_hybrid_dev: pinned core buffer allocation failed");
+            }
+            c->core_bytes = want;
+        }
+        char* h_dev = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer((void**)&h_dev, c->h_core, 0));
+        int* d_core;
+        int rcf;
+        if ((rcf = ws(c, "hc_core", (size_t)cs, &d_core))) return rcf;
+        std::memcpy(c->h_core, core, (size_t)cs * sizeof(int));
+        HIPCHK(c, hipMemcpyAsync(d_core, c->h_core, (size_t)cs * sizeof(int), hipMemcpyHostToDevice, s0));
+        HIPCHK(c, scc_launch_hc_gather_core(P, f32, N, d_core, cs, (double*)(h_dev + id_bytes), s0));
+        HIPCHK(c, hipStreamSynchronize(s0));
+        std::memcpy(block, c->h_core + id_bytes, blk_bytes);
+        return SCC_OK;
+    };
+    std::string err;
+    try {
+        rc = scc_cl::cutree_hybrid(merge, height, N, fetch, deep_split, min_cluster_size, labels, cut_height, err);
+    } catch (const std::bad_alloc&) {
+        return fail(c, SCC_ERR_OOM, "scc_cutree_hybrid_dev: host allocation failed");
+    }
+    if (rc != SCC_OK && !err.empty()) return fail(c, rc, err);
+    return rc;
 }
 
 extern "C" int scc_last_pca_scores(const scc_ctx* c, double* scores, int32_t* ncomp)

@@ -91,6 +91,11 @@ struct scc_ctx {
     // pageable host buffer): 2 slots of dstage_bytes each
     char* h_dstage = nullptr;
     size_t dstage_bytes = 0;
+    // pinned: the tree cut's core ids and core x core distance block
+    // (scc_cutree_hybrid_dev), core_bytes in all
+    char* h_core = nullptr;
+    size_t core_bytes = 0;
+    long long hc_last_scans = 0;  // nearest-neighbour scans of the last scc_hclust_ward_d2_dev
     // sharded PCA (scc_pca_shard_*): this rank's cells and the union width
     int pca_nu = 0, pca_ld = 0;
     int64_t pca_N = 0, pca_clo = 0, pca_chi = 0;

@@ -282,3 +282,24 @@ hipError_t scc_launch_row_hist(const int* rows, long long nnz, int G, unsigned i
 hipError_t scc_launch_first_remap(const unsigned long long* local, int G, const long long* lp2gp,
                                   unsigned long long* global, hipStream_t st);
 }
+
+// ---- device hclust (scc_hclust.hip) -----------------------------------------
+// The NN-chain's state between two launches of one call (device memory).
+#define SCC_HC_ERR_CAP 1    // a loop cap was passed (one extension: n scans; one call: 3 n scans)
+#define SCC_HC_ERR_STATE 2  // the state or the chain holds an index out of range
+struct scc_hc_state {
+    int start;  // lowest active node
+    int tip;    // chain length
+    int step;   // merges done
+    int err;    // SCC_HC_ERR_*: every later launch returns at once
+    long long scans;  // nearest-neighbour scans so far
+};
+extern "C" {
+hipError_t scc_launch_hc_init(int N, scc_hc_state* S, double* size, uint8_t* act, unsigned int* nonfinite,
+                              hipStream_t st);
+hipError_t scc_launch_hc_expand(const void* P, int f32, int N, double* D, unsigned int* nonfinite, hipStream_t st);
+hipError_t scc_launch_hc_chain(double* D, int N, scc_hc_state* S, int* chain, double* size, uint8_t* act, int* out_a,
+                               int* out_b, double* out_h, int max_merges, hipStream_t st);
+hipError_t scc_launch_hc_gather_core(const void* P, int f32, int N, const int* core, int cs, double* block,
+                                     hipStream_t st);
+}

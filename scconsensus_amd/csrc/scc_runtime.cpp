@@ -120,6 +120,7 @@ extern "C" void scc_ctx_destroy(scc_ctx* c)
     if (c->ev_genes) hipEventSynchronize(c->ev_genes), hipEventDestroy(c->ev_genes);
     if (c->h_genes) hipHostFree(c->h_genes);
     if (c->h_dstage) hipHostFree(c->h_dstage);
+    if (c->h_core) hipHostFree(c->h_core);
     hipEventDestroy(c->ev_fork);
     hipEventDestroy(c->ev_join);
     for (int i = 0; i < 2; ++i) {
