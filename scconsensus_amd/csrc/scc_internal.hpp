@@ -1,5 +1,5 @@
 // scc_internal.hpp — runtime-internal state shared by the C ABI translation
-// units (scc_runtime.cpp: context/dataset/DE; scc_distance.cpp: stage 3).
+// units (scc_runtime.cpp: context/dataset; scc_de.cpp: DE; scc_distance.cpp: stage 3).
 #pragma once
 #include "scc.h"
 #include "scc_kernels.hpp"
@@ -29,7 +29,8 @@ constexpr int kScatterCC = 8;      // count chunks per ingest scatter chunk (at 
 constexpr int kSelectCap = 2048;   // per-pair records sorted in LDS
 constexpr int kUnionCap = 4096;
 constexpr int kMaxK = SCC_MAX_K;  // 7-bit cluster codes in the rank kernels: clusters per engine run
-constexpr int kGroupMax = 64;     // K > 2 * kGroupMax: group-pair runs of <= 2 * kGroupMax clusters
+constexpr int64_t kCsrMaxGenes = 262144;  // genes the CSR transpose takes (scc_csr.hip: CT_GMAX)
+constexpr int kGroupMax = 64;    // K > 2 * kGroupMax: group-pair runs of <= 2 * kGroupMax clusters
 
 struct Timer {
     double ms = 0.0;
@@ -285,6 +286,13 @@ inline hipEvent_t ev_take(scc_ctx* c)
 // a residue left by a call outside the engine or a deliberate probe must not
 // be reported by the next kernel launch's hipGetLastError()).
 void scc_enter(const scc_ctx* c);
+
+// frees a dataset's gene-major mirror (scc_runtime.cpp; the DE driver builds it)
+void mirror_free(const scc_dataset* d);
+
+// which ingest the calling thread's last DE run took (scc_diag_ingest_last_path;
+// per thread: a device-list run has one host thread per device)
+extern thread_local int g_ingest_last_path;
 
 // after a synchronisation: the eigensolver flag an earlier device-output
 // scc_distance (which returns without synchronising) left in h_flag

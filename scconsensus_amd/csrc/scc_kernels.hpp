@@ -1,5 +1,5 @@
 // scc_kernels.hpp — internal launcher interface between the runtime
-// (scc_runtime.cpp) and the HIP kernel translation units.
+// (scc_runtime.cpp, scc_de.cpp) and the HIP kernel translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""numpy model of libscc's group-pair runs (scc_runtime.cpp de_run_grouped):
+"""numpy model of libscc's group-pair runs (scc_de.cpp de_run_grouped):
 more consensus clusters than one engine run ranks (128) are cut into
 ceil(K / gmax) balanced groups, the engine runs once per group pair (u < v) on
 the cells of those clusters (others coded -1), and each global pair (i, j) is

@@ -3,7 +3,7 @@
 * An engine-kept distance (device_out_ptr=0, the eigensolver's hand-off flag
   left pending in the context's mapped pinned word) followed by a DE run whose
   host tables outgrow the pinned table buffer: the regrow must not free the
-  flag word (round-3 ADVICE, scc_runtime.cpp), and the flag must still be
+  flag word (round-3 ADVICE, scc_de.cpp), and the flag must still be
   reported and the context destroyed cleanly.
 * ``Engine.de_distance(test="t")`` runs the t test, as ``de_run`` does.
 """

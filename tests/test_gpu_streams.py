@@ -73,3 +73,19 @@ def test_lean_count_matches_full_count(eng, window, monkeypatch):
     full = eng.de_run(ds, code, K, nat.SCC_DE_FAST, fetch="rows")
     for r in (lean, hist, full):
         _same(r, first)
+
+
+def test_rank_log_changes_no_result(eng, monkeypatch, capfd):
+    """SCC_RANK_LOG=1 (the rank stage's work lists, read back after the cross
+    terms) reports one line on stderr and leaves every field as it is."""
+    d = synth.generate("A", G=1000, N=1500, K=6, seed=43)
+    names, code = api.select_clusters(d.labels, 10)
+    K = len(names)
+    ds = eng.dataset_csc(d.indptr, d.indices, d.data, d.G, d.N)
+    plain = eng.de_run(ds, code, K, nat.SCC_DE_FAST, fetch="rows")
+    capfd.readouterr()
+    monkeypatch.setenv("SCC_RANK_LOG", "1")
+    logged = eng.de_run(ds, code, K, nat.SCC_DE_FAST, fetch="rows")
+    err = capfd.readouterr().err
+    _same(logged, plain)
+    assert sum(line.startswith("[scc rank] items ") for line in err.splitlines()) == 1, err

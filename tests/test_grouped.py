@@ -1,5 +1,5 @@
 """The group-pair decomposition libscc uses past 128 clusters
-(tests/group_model.py mirrors scc_runtime.cpp de_run_grouped), with the
+(tests/group_model.py mirrors scc_de.cpp de_run_grouped), with the
 oracle standing in for the device: the runs reassembled in (i, j) order equal
 one oracle run over all K, FAST (rows, order, union) and SLOW (per-pair
 vectors, de flags, union).  tests/test_gpu_grouped.py runs the engine's
