@@ -396,6 +396,51 @@ SCC_API int scc_cutree_hybrid_dev(scc_ctx* ctx, const int32_t* merge, const doub
                                   const void* dist, int32_t dist_f32, int32_t deep_split, int32_t min_cluster_size,
                                   int32_t* labels, double* cut_height);
 
+/* ---- the same two from the PCA scores, no N x N matrix -------------------
+ * The third route (opt-in) to cellTree and dynamicColors, for cell counts whose
+ * packed distance (4 n^2 bytes) or its working copy (8 n^2 bytes) fit nowhere.
+ * The distance is dist() of the [n][16] scores, and Ward linkage on Euclidean
+ * points needs only centroids and sizes: 2 |A| |B| / (|A| + |B|) |cA - cB|^2 is
+ * the squared dissimilarity the Lance-Williams update carries, a merge is a
+ * weighted mean.  Device memory: 128 bytes of centroid per cell plus ~40 bytes
+ * of chain state (scc_hclust_vec.hip).
+ *
+ * Where it differs from the host and the device route: the chain is the same
+ * (restart, scan order, lowest index on a tie, the larger index survives), the
+ * rounding is not.  It returns their tree (merge and order equal, heights
+ * within a few ulp) whenever no two candidate dissimilarities lie within
+ * rounding of each other; on exact ties (duplicate cells, lattices) it returns
+ * a valid Ward tree that may resolve the tie differently.
+ *
+ * scc_pca_scores: the PCA half of scc_distance(SCC_DIST_PCA_EUCLID), stopping
+ * before the dist kernel: it never allocates the n (n - 1) / 2 outputs.  The
+ * [n][16] scores are kept where scc_distance keeps them (scc_last_pca_scores
+ * returns the same bits after either call on the same input); any engine-kept
+ * distance is dropped, so a later NULL-distance call (scc_silhouette,
+ * scc_hclust_ward_d2_dev, scc_cutree_hybrid_dev) fails with SCC_ERR_INVALID.
+ * Runs on devices[0] only. */
+SCC_API int scc_pca_scores(scc_ctx* ctx, const scc_dataset* ds, const int32_t* genes /* host */, int32_t n_union,
+                           int32_t ncomp);
+/* hclust(dist(scores), "ward.D2").  scores: device pointer to [n][16] doubles, unused
+ * components zero (as scc_distance_scores takes them), read only; NULL = the kept scores
+ * of the last scc_pca_scores / PCA scc_distance.  merge/height/order: host, as
+ * scc_hclust_ward_d2.  SCC_ERR_NONFINITE: a non-finite score; SCC_ERR_INVALID: no kept
+ * scores, or scores of another size; SCC_ERR_HIP: the chain passed a loop cap.
+ * One nearest-neighbour scan is two launches (a grid over the nodes,
+ * SCC_HCLUST_VEC_SCAN_NODES per workgroup, then one workgroup that steps the chain); the
+ * host queues SCC_HCLUST_VEC_SCANS_PER_BATCH scans, reads the state and queues the next
+ * batch until the last merge (timer family "hclust_vec", one entry per launch). */
+#define SCC_HCLUST_VEC_SCAN_NODES 512
+#define SCC_HCLUST_VEC_SCANS_PER_BATCH 1024
+SCC_API int scc_hclust_ward_d2_scores(scc_ctx* ctx, int64_t n, const void* scores, int32_t* merge, double* height,
+                                      int32_t* order);
+/* scc_cutree_hybrid_dev with distM[core, core] computed from the scores (same NULL rule as
+ * scc_hclust_ward_d2_scores) with the dist kernel's arithmetic: the values the packed f64
+ * vector would hold, so the labels are those of the other routes for the same tree. */
+SCC_API int scc_cutree_hybrid_scores(scc_ctx* ctx, const int32_t* merge, const double* height, int64_t n,
+                                     const void* scores, int32_t deep_split, int32_t min_cluster_size,
+                                     int32_t* labels, double* cut_height);
+
 /* ---- diagnostics (tests): the PCA eigensolver's parts on device pointers --
  * Not on the R path.  Each synchronises the device and returns 0 on success.
  *   scc_diag_eigen_topk   top-k eigenpairs of a device n x n symmetric A (lda)
@@ -415,8 +460,9 @@ SCC_API int scc_diag_eig_last_path(void);
  * SCC_INGEST_FULL=1), 2 the lean transpose of a validated dataset, 3 the
  * regroup of the dataset's gene-major mirror. */
 SCC_API int scc_diag_ingest_last_path(void);
-/* Nearest-neighbour scans (one row each) of the context's last
- * scc_hclust_ward_d2_dev, for bandwidth figures; -1 without a context. */
+/* Nearest-neighbour scans (one row each; one pass over the centroids each) of
+ * the context's last scc_hclust_ward_d2_dev or scc_hclust_ward_d2_scores, for
+ * bandwidth figures; -1 without a context. */
 SCC_API int64_t scc_diag_hclust_last_scans(const scc_ctx* ctx);
 /* s_memtime stamps of the last scc_diag_small_syev's phases [8] */
 SCC_API int scc_diag_small_syev_stamps(unsigned long long* out);

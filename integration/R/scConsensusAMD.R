@@ -112,6 +112,36 @@
   list(tree = tree, colors = colors)
 }
 
+# options(scConsensus.engineTree = "scores"): no distance at all.  The engine
+# stops after the PCA (Fast:398-399, slow:234-235) and keeps the N x 15 scores;
+# hclust(ward.D2) runs on centroids of the scores and the hybrid cuts compute
+# their distM entries from them (128 bytes per cell instead of 8 N^2: the only
+# route at cell counts whose matrix fits nowhere).  The same tree as the other
+# engine routes whenever no two candidate dissimilarities lie within rounding
+# of each other; on exact ties (duplicate cells) a valid Ward tree that may
+# resolve the tie differently.  deepSplitInfo's SI (Fast:433, computed and
+# discarded by the reference) is not computed: this route makes no C_scc_si
+# call; Fast:433's stop for fewer than 2 groups is kept.
+.scc_tree_from_scores <- function() identical(getOption("scConsensus.engineTree", FALSE), "scores")
+
+.scc_tree_and_colors_scores <- function(h, genes, n_cells, deepSplitValues, minClusterSize, with_si) {
+  .Call("C_scc_pca_scores", h, as.integer(genes), 0L)
+  t <- .Call("C_scc_hclust_scores", as.integer(n_cells))
+  tree <- structure(list(merge = t[[1]], height = t[[2]], order = t[[3]], labels = NULL,
+                         method = "ward.D2", call = match.call(), dist.method = "euclidean"),
+                    class = "hclust")
+  colors <- list()
+  for (dsv in deepSplitValues) {
+    grp <- .Call("C_scc_cutree_scores", tree$merge, as.double(tree$height), as.integer(dsv), as.integer(minClusterSize))
+    colors[[paste("deepsplit:", dsv)]] <- WGCNA::labels2colors(grp)
+    # silhouette() of fewer than 2 (or of n) groups is NA and Fast:433 stops on it
+    k <- length(unique(grp))
+    if (with_si && (k < 2L || k >= n_cells)) stop("$ operator is invalid for atomic vectors")
+  }
+  names(colors) <- paste("deepsplit:", deepSplitValues)
+  list(tree = tree, colors = colors)
+}
+
 reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method = "wilcox",
                                      qValThrs = 0.1, logFCThrs = 0.5, deepSplitValues = 1:4,
                                      minClusterSize = 10, minPerCent = 20,
@@ -131,7 +161,9 @@ reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method 
                as.integer(NumbertopDEGenes), match(method, tests) - 1L)
   deGeneUnion <- rownames(dataMatrix)[res[[1]]]
   print(str(deGeneUnion))
-  tc <- if (.scc_tree_on_device()) {
+  tc <- if (.scc_tree_from_scores()) {
+    .scc_tree_and_colors_scores(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = TRUE)
+  } else if (.scc_tree_on_device()) {
     .scc_tree_and_colors_dev(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = TRUE)
   } else {
     d <- .scc_dist(h, res[[1]], ncol(dataMatrix))
@@ -176,7 +208,9 @@ reclusterDEConsensus <- function(dataMatrix, consensusClusterLabels, method = "W
   deGeneUnion <- rownames(dataMatrix)[res[[1]]]
   print(str(deGeneUnion))
   saveRDS(deGeneUnion, file = "deGeneUnion.rds")
-  tc <- if (.scc_tree_on_device()) {
+  tc <- if (.scc_tree_from_scores()) {
+    .scc_tree_and_colors_scores(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = FALSE)
+  } else if (.scc_tree_on_device()) {
     .scc_tree_and_colors_dev(h, res[[1]], ncol(dataMatrix), deepSplitValues, minClusterSize, with_si = FALSE)
   } else {
     d <- .scc_dist(h, res[[1]], ncol(dataMatrix))

@@ -25,6 +25,10 @@
  *                   stays in the engine (Fast:398-400), the tree (Fast:406-411,
  *                   slow:242-247) and the cuts (Fast:421-427, slow:257-263) are
  *                   computed on it there; no "dist" object reaches R
+ *   C_scc_pca_scores, C_scc_hclust_scores, C_scc_cutree_scores
+ *                   options(scConsensus.engineTree = "scores"): the engine stops
+ *                   after the PCA (Fast:398-399) and keeps the scores; the tree
+ *                   and the cuts are computed from them, no distance exists
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -376,6 +380,63 @@ SEXP C_scc_cutree_dev(SEXP merge, SEXP height, SEXP deep, SEXP minsize)
     return lab;
 }
 
+/* The PCA half of C_scc_distance alone (scc_pca_scores): the scores stay in the
+ * engine for C_scc_hclust_scores / C_scc_cutree_scores, no distance is computed
+ * or kept: returns the cell count */
+SEXP C_scc_pca_scores(SEXP h, SEXP genes, SEXP ncomp)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes);
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int k = 0; k < nu; ++k) {
+        g0[k] = INTEGER(genes)[k] - 1;
+        if (g0[k] < 0 || g0[k] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[k] + 1);
+    }
+    check(scc_pca_scores(g_ctx, ds, g0, nu, Rf_asInteger(ncomp)));
+    return Rf_ScalarInteger(N);
+}
+
+/* hclust(dist(scores), "ward.D2") from the engine-kept scores of n cells
+ * (scc_hclust_ward_d2_scores: no N x N matrix anywhere) */
+SEXP C_scc_hclust_scores(SEXP n_cells)
+{
+    ensure_ctx();
+    const int64_t n = Rf_asInteger(n_cells);
+    if (n < 2) Rf_error("scConsensus engine: hclust needs at least two cells");
+    SEXP merge = PROTECT(Rf_allocMatrix(INTSXP, (int)(n - 1), 2));
+    SEXP height = PROTECT(Rf_allocVector(REALSXP, n - 1));
+    SEXP order = PROTECT(Rf_allocVector(INTSXP, n));
+    const int rc = scc_hclust_ward_d2_scores(g_ctx, n, NULL, INTEGER(merge), REAL(height), INTEGER(order));
+    if (rc != SCC_OK) {
+        UNPROTECT(3);
+        check(rc);
+    }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, merge);
+    SET_VECTOR_ELT(out, 1, height);
+    SET_VECTOR_ELT(out, 2, order);
+    UNPROTECT(4);
+    return out;
+}
+
+/* C_scc_cutree with distM computed from the engine-kept scores (scc_cutree_hybrid_scores) */
+SEXP C_scc_cutree_scores(SEXP merge, SEXP height, SEXP deep, SEXP minsize)
+{
+    ensure_ctx();
+    const int64_t n = (int64_t)XLENGTH(height) + 1;
+    if (XLENGTH(merge) != 2 * (n - 1))
+        Rf_error("scConsensus engine: merge / height do not match (%lld cells)", (long long)n);
+    SEXP m = PROTECT(Rf_coerceVector(merge, INTSXP));
+    SEXP lab = PROTECT(Rf_allocVector(INTSXP, n));
+    const int rc = scc_cutree_hybrid_scores(g_ctx, INTEGER(m), REAL(height), n, NULL, Rf_asInteger(deep),
+                                            Rf_asInteger(minsize), INTEGER(lab), NULL);
+    UNPROTECT(2);
+    check(rc);
+    return lab;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"C_scc_dataset", (DL_FUNC)&C_scc_dataset, 4},
     {"C_scc_release", (DL_FUNC)&C_scc_release, 1},
@@ -389,6 +450,9 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_distance_dev", (DL_FUNC)&C_scc_distance_dev, 4},
     {"C_scc_hclust_dev", (DL_FUNC)&C_scc_hclust_dev, 1},
     {"C_scc_cutree_dev", (DL_FUNC)&C_scc_cutree_dev, 4},
+    {"C_scc_pca_scores", (DL_FUNC)&C_scc_pca_scores, 3},
+    {"C_scc_hclust_scores", (DL_FUNC)&C_scc_hclust_scores, 1},
+    {"C_scc_cutree_scores", (DL_FUNC)&C_scc_cutree_scores, 4},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

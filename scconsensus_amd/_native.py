@@ -34,6 +34,8 @@ SCC_DIST_PEARSON = 1
 SCC_PTR_HOST = 0
 SCC_PTR_DEVICE = 1
 HCLUST_MERGES_PER_LAUNCH = 1024  # SCC_HCLUST_MERGES_PER_LAUNCH: merges per chain launch of hclust_ward_d2_dev
+HCLUST_VEC_SCAN_NODES = 512  # SCC_HCLUST_VEC_SCAN_NODES: nodes a scan workgroup of hclust_ward_d2_scores owns
+HCLUST_VEC_SCANS_PER_BATCH = 1024  # SCC_HCLUST_VEC_SCANS_PER_BATCH: scans (two launches each) between state reads
 
 # every symbol include/scc.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -47,6 +49,7 @@ EXPORTS = [
     "scc_distance", "scc_de_distance", "scc_distance_cols", "scc_pca_shard_colsum", "scc_pca_shard_gram", "scc_pca_shard_scores", "scc_pca_shard_eigen", "scc_pca_shard_project",
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
+    "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_hclust_last_scans",
     "scc_diag_small_syev_stamps", "scc_diag_pvalues",
@@ -143,6 +146,9 @@ def load():
         "scc_cutree_hybrid": (ctypes.c_int, [vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
         "scc_hclust_ward_d2_dev": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, vp]),
         "scc_cutree_hybrid_dev": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, i32, vp, P(dbl)]),
+        "scc_pca_scores": (ctypes.c_int, [vp, vp, vp, i32, i32]),
+        "scc_hclust_ward_d2_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp]),
+        "scc_cutree_hybrid_scores": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
         "scc_diag_hclust_last_scans": (i64, [vp]),
         "scc_diag_eigen_topk": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, P(ctypes.c_int)]),
         "scc_diag_small_syev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp]),
@@ -599,8 +605,47 @@ class Engine:
                                                    ctypes.byref(cut)))
         return lab, cut.value
 
+    def pca_scores(self, ds: Dataset, genes, ncomp=0):
+        """The PCA half of distance(): the [N][16] scores stay in the engine
+        (last_pca_scores reads them), no distance is computed or kept."""
+        genes = np.ascontiguousarray(genes, np.int32)
+        self._check(self.lib.scc_pca_scores(self.ctx, ds.handle, _ptr(genes), len(genes), ncomp))
+
+    def hclust_ward_d2_scores(self, N, scores_device_ptr=None):
+        """hclust(dist(scores), "ward.D2") from a device [N][16] score matrix
+        (the engine-kept scores unless a device pointer is given), without
+        the N x N matrix: (merge, height, order) as hclust_ward_d2.  The tree
+        of the matrix routes whenever no two candidate dissimilarities lie
+        within rounding of each other; on exact ties a valid Ward tree that
+        may resolve the tie differently."""
+        N = int(N)
+        if N < 2:
+            raise ValueError("hclust_ward_d2_scores needs at least two observations")
+        merge = np.zeros(2 * (N - 1), np.int32)
+        height = np.zeros(N - 1)
+        order = np.zeros(N, np.int32)
+        self._check(self.lib.scc_hclust_ward_d2_scores(self.ctx, N, ctypes.c_void_p(scores_device_ptr or None),
+                                                       _ptr(merge), _ptr(height), _ptr(order)))
+        return merge.reshape(2, N - 1).T.copy(), height, order
+
+    def cutree_hybrid_scores(self, merge, height, deep_split, min_cluster_size, scores_device_ptr=None):
+        """cutree_hybrid with distM computed from a device [N][16] score matrix
+        (same rule as hclust_ward_d2_scores): (labels, cut height)."""
+        merge = np.asarray(merge)
+        n = merge.shape[0] + 1
+        m = np.ascontiguousarray(merge.T.reshape(-1), np.int32)
+        h = np.ascontiguousarray(height, np.float64)
+        if h.shape != (n - 1,):
+            raise ValueError("shape mismatch between merge and height")
+        lab = np.zeros(n, np.int32)
+        cut = ctypes.c_double()
+        self._check(self.lib.scc_cutree_hybrid_scores(self.ctx, _ptr(m), _ptr(h), n,
+                                                      ctypes.c_void_p(scores_device_ptr or None), int(deep_split),
+                                                      int(min_cluster_size), _ptr(lab), ctypes.byref(cut)))
+        return lab, cut.value
+
     def hclust_last_scans(self):
-        """Nearest-neighbour scans of the last hclust_ward_d2_dev (diagnostics)."""
+        """Nearest-neighbour scans of the last hclust_ward_d2_dev or hclust_ward_d2_scores (diagnostics)."""
         return int(self.lib.scc_diag_hclust_last_scans(self.ctx))
 
     def last_pca_scores(self, N):

@@ -19,8 +19,14 @@ keeps them there (libscc's host functions scc_hclust_ward_d2 /
 scc_cutree_hybrid).  With ``tree="device"`` (opt-in) the
 distance stays in HBM and the tree and the cuts are computed on it there
 (scc_hclust_ward_d2_dev / scc_cutree_hybrid_dev: the same results bit for
-bit, no host copy of the distance).  The ComplexHeatmap plot is not part of
-this engine; ``plotName`` is ignored.
+bit, no host copy of the distance).  With ``tree="scores"`` (opt-in) no
+distance is computed at all: the tree and the cuts come from the N x 15 PCA
+scores (scc_pca_scores / scc_hclust_ward_d2_scores / scc_cutree_hybrid_scores),
+for cell counts whose N x N matrix fits nowhere.  That route returns the same
+tree whenever no two candidate dissimilarities lie within rounding of each
+other; on exact ties (duplicate cells) it returns a valid Ward tree that may
+resolve the tie differently.  The ComplexHeatmap plot is not part of this
+engine; ``plotName`` is ignored.
 """
 from __future__ import annotations
 
@@ -144,13 +150,32 @@ def _hclust_ward_d2_dev(eng, N):
     return {"merge": merge, "height": height, "order": order, "method": "ward.D2", "dist.method": "euclidean"}
 
 
+def _hclust_ward_d2_scores(eng, N):
+    """The tree from the engine-kept PCA scores (tree="scores")."""
+    merge, height, order = eng.hclust_ward_d2_scores(N)
+    return {"merge": merge, "height": height, "order": order, "method": "ward.D2", "dist.method": "euclidean"}
+
+
 def _check_tree(tree):
-    if tree not in ("host", "device"):
-        raise ValueError(f"tree must be 'host' or 'device', not {tree!r}")
+    if tree not in ("host", "device", "scores"):
+        raise ValueError(f"tree must be 'host', 'device' or 'scores', not {tree!r}")
     return tree == "device"
 
 
-def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None, info=None, cut_eng=None):
+def _distance_and_tree(eng, ds, uni, N, tree):
+    """Fast:398-411, slow:234-247: (d, cellTree).  d is the packed host vector
+    for tree="host" and None otherwise (tree="device": it stays in the engine;
+    tree="scores": it is never computed)."""
+    if tree == "scores":
+        eng.pca_scores(ds, uni)
+        return None, _hclust_ward_d2_scores(eng, N)
+    on_device = tree == "device"
+    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID, device_out_ptr=0 if on_device else None)
+    return d, (_hclust_ward_d2_dev(eng, N) if on_device else _hclust_ward_d2(d, N))
+
+
+def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None, info=None, cut_eng=None,
+                    scores_eng=None):
     """Fast:418-431: cutreeDynamic(dendro, distM = as.matrix(d), deepSplit = dsv,
     pamStage = FALSE, minClusterSize) -> labels2colors, named "deepsplit: dsv".
     With ``eng`` (FAST, which computes the silhouette for every deepSplit):
@@ -160,11 +185,15 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
     summary(cluster::silhouette(groups, as.matrix(d)))$clus.avg.widths), the
     silhouette computed by the engine on its HBM-resident copy of d.
     With ``cut_eng`` the cut reads that HBM-resident copy too (dist_packed is
-    not used)."""
+    not used).  With ``scores_eng`` there is no distance: the cut computes its
+    distM entries from the engine-kept scores and the rows' SI is None (the
+    silhouette from the scores is not part of this route)."""
     out = {}
     N = len(tree["order"])
     for dsv in deepSplitValues:
-        if cut_eng is not None:
+        if scores_eng is not None:
+            lab, _ = scores_eng.cutree_hybrid_scores(tree["merge"], tree["height"], int(dsv), int(minClusterSize))
+        elif cut_eng is not None:
             lab, _ = cut_eng.cutree_hybrid_dev(tree["merge"], tree["height"], int(dsv), int(minClusterSize))
         else:
             lab, _ = nat.cutree_hybrid(tree["merge"], tree["height"], dist_packed, int(dsv), int(minClusterSize))
@@ -177,8 +206,8 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
                 raise RuntimeError("$ operator is invalid for atomic vectors (silhouette of "
                                    f"{k} group(s) at deepSplit {dsv}, Fast:433)")
             if info is not None:  # the SI the reference computes and discards
-                info.append({"DeepSplit": dsv, "NumbersOfClusters": k,
-                             "SI": float(np.mean(eng.silhouette(N, lab)[1]))})
+                si = None if scores_eng is not None else float(np.mean(eng.silhouette(N, lab)[1]))
+                info.append({"DeepSplit": dsv, "NumbersOfClusters": k, "SI": si})
     return out
 
 
@@ -219,13 +248,14 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
     print(f" chr [1:{len(uni)}] " + " ".join(f'"{g}"' for g in gnames[uni[:5]]) + (" ..." if len(uni) > 5 else ""))
     if len(uni) == 0:
         raise RuntimeError("no DE genes (R fails on an empty deGenes data frame, Fast:386)")
-    # tree="device": the distance stays in the engine (d is None), the tree, the cuts and the silhouette read it there
-    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID, device_out_ptr=0 if on_device else None)
-    cell_tree = _hclust_ward_d2_dev(eng, N) if on_device else _hclust_ward_d2(d, N)
+    # tree="device": the distance stays in the engine (d is None), the tree, the cuts and the silhouette read it there;
+    # tree="scores": no distance, the tree and the cuts read the engine-kept scores
+    d, cell_tree = _distance_and_tree(eng, ds, uni, N, tree)
     info = [] if return_details else None  # deepSplitInfo: computed by the reference, never returned (Fast:433)
     ret = {"deGeneUnion": list(gnames[uni]), "cellTree": cell_tree,
            "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize, eng, info,
-                                            cut_eng=eng if on_device else None)}
+                                            cut_eng=eng if on_device else None,
+                                            scores_eng=eng if tree == "scores" else None)}
     if save:
         _save(ret, filename)
     if return_details:
@@ -274,11 +304,11 @@ def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", 
     uni = res.union
     if len(uni) == 0:
         raise RuntimeError("empty DE gene union")
-    d = eng.distance(ds, uni, nat.SCC_DIST_PCA_EUCLID, device_out_ptr=0 if on_device else None)
-    cell_tree = _hclust_ward_d2_dev(eng, N) if on_device else _hclust_ward_d2(d, N)
+    d, cell_tree = _distance_and_tree(eng, ds, uni, N, tree)
     ret = {"deGeneUnion": list(gnames[uni]), "cellTree": cell_tree,
            "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize,
-                                            cut_eng=eng if on_device else None)}
+                                            cut_eng=eng if on_device else None,
+                                            scores_eng=eng if tree == "scores" else None)}
     if save:
         _save({"qValueList": qlist, "logFCList": lflist, "deGeneList": delist}, "de_lists")
         _save(ret, filename)

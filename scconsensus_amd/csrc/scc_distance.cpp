@@ -302,11 +302,17 @@ static int genes_h2d(scc_ctx* c, int* d_genes, const int32_t* genes, int nu, hip
 // set by scc_de_distance around its distance call: the DE's device union
 static thread_local const int* t_dev_union = nullptr;
 
+// dist_impl's out_kind for scc_pca_scores: the PCA half only, no distance
+// output anywhere (devices[0] alone, whatever the device list)
+#define SCC_PTR_NONE (-1)
+
 static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, int32_t nu, int32_t metric,
                      int32_t ncomp, int64_t col_lo, int64_t col_hi, void* dist_out, int32_t out_kind, int32_t out_f32)
 {
     if (!c || !ds || !genes) return fail(c, SCC_ERR_INVALID, "scc_distance: null argument");
-    if (!dist_out && out_kind != SCC_PTR_DEVICE) return fail(c, SCC_ERR_INVALID, "scc_distance: null output");
+    const bool scores_only = out_kind == SCC_PTR_NONE;
+    if (!dist_out && out_kind != SCC_PTR_DEVICE && !scores_only) return fail(c, SCC_ERR_INVALID, "scc_distance: null output");
+    if (scores_only && metric != SCC_DIST_PCA_EUCLID) return fail(c, SCC_ERR_INVALID, "scc_pca_scores: PCA metric only");
     if (ds->ctx != c) return fail(c, SCC_ERR_INVALID, "dataset belongs to another context");
     if (nu < 1) return fail(c, SCC_ERR_INVALID, "empty gene union");
     if (metric != SCC_DIST_PCA_EUCLID && metric != SCC_DIST_PEARSON) return fail(c, SCC_ERR_INVALID, "bad metric");
@@ -340,7 +346,7 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
     const int nchunk_mean = 512;  // 2 x 512 workgroups over the column sums
     if ((rc = ws_get(c, "d_part", sizeof(double) * 2 * (size_t)nchunk_mean * ld, &d_part))) return rc;
     void* d_out = dist_out;
-    if (out_kind == SCC_PTR_HOST || !dist_out) {  // NULL device output: keep it in the workspace
+    if (!scores_only && (out_kind == SCC_PTR_HOST || !dist_out)) {  // NULL device output: keep it in the workspace
         if ((rc = ws_get(c, "d_dist", npairs * (out_f32 ? 4 : 8), &d_out))) return rc;
     }
     // scc_de_distance: the DE's union is still in the workspace, on this device
@@ -432,7 +438,9 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
         auto emit = [&](int64_t a, int64_t b, void* dst) {
             return scc_launch_dist_euclid(d_P, N, (int)a, (int)b, dst, out_f32, s0);
         };
-        if (!c->peers.empty()) {
+        if (scores_only) {
+            // scc_pca_scores stops here: the scores stay in the workspace
+        } else if (!c->peers.empty()) {
             const SliceLaunch launch = [&](const void* pay, int64_t a, int64_t b, void* dst, hipStream_t st) {
                 return scc_launch_dist_euclid((const double*)pay, N, (int)a, (int)b, dst, out_f32, st);
             };
@@ -509,7 +517,7 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
         else
             HIPCHK(c, hipMemcpyAsync(&c->eig_err, d_eig_err, sizeof(unsigned int), hipMemcpyDeviceToHost, s0));
     }
-    const bool own = out_kind == SCC_PTR_HOST || !dist_out;
+    const bool own = !scores_only && (out_kind == SCC_PTR_HOST || !dist_out);
     c->d_last_dist = (own && col_lo == 0 && col_hi == N) ? d_out : nullptr;
     c->last_dist_n = N;
     c->last_dist_f32 = out_f32 ? 1 : 0;
@@ -542,6 +550,13 @@ extern "C" int scc_distance(scc_ctx* c, const scc_dataset* ds, const int32_t* ge
                             int32_t ncomp, void* dist_out, int32_t out_kind, int32_t out_f32)
 {
     return dist_impl(c, ds, genes, nu, metric, ncomp, 0, ds ? ds->N : 0, dist_out, out_kind, out_f32);
+}
+
+extern "C" int scc_pca_scores(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, int32_t nu, int32_t ncomp)
+{
+    const int rc = dist_impl(c, ds, genes, nu, SCC_DIST_PCA_EUCLID, ncomp, 0, ds ? ds->N : 0, nullptr, SCC_PTR_NONE, 0);
+    if (rc != SCC_OK && c) c->d_last_scores = nullptr;  // (a failed eigensolve leaves no scores to read)
+    return rc;
 }
 
 extern "C" int scc_de_distance(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_t K,
@@ -1008,6 +1023,168 @@ extern "C" int scc_cutree_hybrid_dev(scc_ctx* c, const int32_t* merge, const dou
         rc = scc_cl::cutree_hybrid(merge, height, N, fetch, deep_split, min_cluster_size, labels, cut_height, err);
     } catch (const std::bad_alloc&) {
         return fail(c, SCC_ERR_OOM, "scc_cutree_hybrid_dev: host allocation failed");
+    }
+    if (rc != SCC_OK && !err.empty()) return fail(c, rc, err);
+    return rc;
+}
+
+// ---- hclust(ward.D2) and the tree cut from the PCA scores --------------------
+// (kernels and algorithm: scc_hclust_vec.hip; post-processing and the cut
+// itself: scc_cluster.cpp, shared with the other two routes)
+
+// What NULL `scores` stands for: the [N][16] scores the last scc_pca_scores or
+// PCA scc_distance kept in the workspace.
+static int kept_scores(scc_ctx* c, int64_t N, const char* who, const double** P)
+{
+    if (!c->d_last_scores || c->last_n != N)
+        return fail(c, SCC_ERR_INVALID, std::string(who) + ": no PCA scores of this size are kept");
+    *P = c->d_last_scores;
+    // a device-output scc_distance returns before its eigensolver flag is read
+    HIPCHK(c, hipStreamSynchronize(c->s0));
+    int rc = check_pending_eig(c);
+    if (rc) {
+        c->d_last_dist = nullptr;
+        c->d_last_scores = nullptr;
+    }
+    return rc;
+}
+
+extern "C" int scc_hclust_ward_d2_scores(scc_ctx* c, int64_t n, const void* scores, int32_t* merge, double* height,
+                                         int32_t* order)
+{
+    if (!c || !merge || !height) return fail(c, SCC_ERR_INVALID, "scc_hclust_ward_d2_scores: null argument");
+    if (n < 2 || n > (int64_t)INT32_MAX) return fail(c, SCC_ERR_INVALID, "scc_hclust_ward_d2_scores: bad cell count");
+    const int N = (int)n;
+    scc_enter(c);
+    hipStream_t s0 = c->s0;
+    const double* P = (const double*)scores;
+    int rc;
+    if (!P && (rc = kept_scores(c, N, "scc_hclust_ward_d2_scores", &P))) return rc;
+    const int nparts = scc_wv_scan_workgroups(N);
+    scc_wv_state* d_state;
+    unsigned int* d_bad;
+    int *d_chain, *d_a, *d_b, *d_pi;
+    double *d_cent, *d_size, *d_h, *d_pv;
+    uint8_t* d_act;
+    if ((rc = ws(c, "wv_state", 1, &d_state))) return rc;
+    if ((rc = ws(c, "hc_bad", 1, &d_bad))) return rc;
+    if ((rc = ws(c, "wv_cent", (size_t)N * 16, &d_cent))) return rc;
+    if ((rc = ws(c, "wv_pv", (size_t)nparts, &d_pv))) return rc;
+    if ((rc = ws(c, "wv_pi", (size_t)nparts, &d_pi))) return rc;
+    if ((rc = ws(c, "hc_chain", (size_t)N, &d_chain))) return rc;
+    if ((rc = ws(c, "hc_a", (size_t)N, &d_a))) return rc;
+    if ((rc = ws(c, "hc_b", (size_t)N, &d_b))) return rc;
+    if ((rc = ws(c, "hc_size", (size_t)N, &d_size))) return rc;
+    if ((rc = ws(c, "hc_h", (size_t)N, &d_h))) return rc;
+    if ((rc = ws(c, "hc_act", (size_t)N, &d_act))) return rc;
+    {
+        Scope sc(c, "hclust_vec_init", s0);
+        HIPCHK(c, scc_launch_wv_init(P, N, d_cent, d_state, d_size, d_act, d_bad, s0));
+    }
+    // the chain is never launched on a non-finite score (a NaN compares false both ways)
+    unsigned int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    if (bad) return fail(c, SCC_ERR_NONFINITE, "scc_hclust_ward_d2_scores: the scores hold a non-finite entry");
+    // batches of scans queued back to back, the state read once per batch: a
+    // call has at most 3 n scans, so the loop is bounded whatever the state says
+    scc_wv_state st{};
+    const long long max_batches = (3ll * N) / SCC_HCLUST_VEC_SCANS_PER_BATCH + 1;
+    for (long long batch = 0; batch < max_batches; ++batch) {
+        for (int k = 0; k < SCC_HCLUST_VEC_SCANS_PER_BATCH; ++k) {
+            {
+                Scope sc(c, "hclust_vec", s0);
+                HIPCHK(c, scc_launch_wv_scan(d_cent, N, d_state, d_size, d_act, d_pv, d_pi, s0));
+            }
+            {
+                Scope sc(c, "hclust_vec", s0);
+                HIPCHK(c, scc_launch_wv_advance(d_cent, N, d_state, d_chain, d_size, d_act, d_pv, d_pi, d_a, d_b, d_h,
+                                                s0));
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(&st, d_state, sizeof(st), hipMemcpyDeviceToHost, s0));
+        HIPCHK(c, hipStreamSynchronize(s0));
+        if (st.err || st.step >= N - 1) break;
+    }
+    c->hc_last_scans = st.scans;
+    if (st.err == SCC_HC_ERR_CAP || (!st.err && st.step != N - 1))
+        return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_scores: the NN-chain passed its scan cap at merge " +
+                                        std::to_string(st.step) + " (corrupt state?)");
+    if (st.err)
+        return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_scores: the NN-chain stopped at merge " + std::to_string(st.step) +
+                                        " with an index out of range");
+    std::vector<int32_t> a((size_t)N - 1), b((size_t)N - 1);
+    std::vector<double> h2((size_t)N - 1);
+    HIPCHK(c, hipMemcpyAsync(a.data(), d_a, sizeof(int32_t) * a.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipMemcpyAsync(b.data(), d_b, sizeof(int32_t) * b.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipMemcpyAsync(h2.data(), d_h, sizeof(double) * h2.size(), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    for (size_t k = 0; k < a.size(); ++k)
+        if (a[k] < 0 || a[k] >= N || b[k] < 0 || b[k] >= N)
+            return fail(c, SCC_ERR_HIP, "scc_hclust_ward_d2_scores: a merge holds a node out of range");
+    try {
+        scc_cl::hclust_finish(N, a.data(), b.data(), h2.data(), merge, height, order);
+    } catch (const std::bad_alloc&) {
+        return fail(c, SCC_ERR_OOM, "scc_hclust_ward_d2_scores: host allocation failed");
+    }
+    return SCC_OK;
+}
+
+// the pinned buffer of a core fetch (ids up, the block back), grown as scc_cutree_hybrid_dev grows it
+static int core_buffer(scc_ctx* c, size_t bytes, const char* who)
+{
+    if (c->core_bytes >= bytes) return SCC_OK;
+    if (c->h_core) hipHostFree(c->h_core);
+    c->h_core = nullptr;
+    c->core_bytes = 0;
+    const size_t want = std::max<size_t>((size_t)1 << 20, 2 * bytes);
+    if (hipHostMalloc((void**)&c->h_core, want, hipHostMallocMapped) != hipSuccess) {
+        hipGetLastError();
+        c->h_core = nullptr;
+        return fail(c, SCC_ERR_OOM, std::string(who) + ": pinned core buffer allocation failed");
+    }
+    c->core_bytes = want;
+    return SCC_OK;
+}
+
+extern "C" int scc_cutree_hybrid_scores(scc_ctx* c, const int32_t* merge, const double* height, int64_t n,
+                                        const void* scores, int32_t deep_split, int32_t min_cluster_size,
+                                        int32_t* labels, double* cut_height)
+{
+    if (!c || !merge || !height || !labels) return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_scores: null argument");
+    if (n < 2 || n > (int64_t)INT32_MAX) return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_scores: bad cell count");
+    const int N = (int)n;
+    scc_enter(c);
+    hipStream_t s0 = c->s0;
+    const double* P = (const double*)scores;
+    int rc;
+    if (!P && (rc = kept_scores(c, N, "scc_cutree_hybrid_scores", &P))) return rc;
+    // distM[core, core] as scc_cutree_hybrid_dev fetches it, the entries
+    // computed from the score rows instead of gathered
+    const scc_cl::CoreFetch fetch = [&](const int32_t* core, int cs, double* block) -> int {
+        for (int i = 0; i < cs; ++i)
+            if (core[i] < 1 || core[i] > N)
+                return fail(c, SCC_ERR_INVALID, "scc_cutree_hybrid_scores: object id out of range");
+        const size_t id_bytes = ((size_t)cs * sizeof(int) + 255) & ~(size_t)255;
+        const size_t blk_bytes = (size_t)cs * (size_t)cs * sizeof(double);
+        int rcf;
+        if ((rcf = core_buffer(c, id_bytes + blk_bytes, "scc_cutree_hybrid_scores"))) return rcf;
+        char* h_dev = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer((void**)&h_dev, c->h_core, 0));
+        int* d_core;
+        if ((rcf = ws(c, "hc_core", (size_t)cs, &d_core))) return rcf;
+        std::memcpy(c->h_core, core, (size_t)cs * sizeof(int));
+        HIPCHK(c, hipMemcpyAsync(d_core, c->h_core, (size_t)cs * sizeof(int), hipMemcpyHostToDevice, s0));
+        HIPCHK(c, scc_launch_wv_gather_core(P, N, d_core, cs, (double*)(h_dev + id_bytes), s0));
+        HIPCHK(c, hipStreamSynchronize(s0));
+        std::memcpy(block, c->h_core + id_bytes, blk_bytes);
+        return SCC_OK;
+    };
+    std::string err;
+    try {
+        rc = scc_cl::cutree_hybrid(merge, height, N, fetch, deep_split, min_cluster_size, labels, cut_height, err);
+    } catch (const std::bad_alloc&) {
+        return fail(c, SCC_ERR_OOM, "scc_cutree_hybrid_scores: host allocation failed");
     }
     if (rc != SCC_OK && !err.empty()) return fail(c, rc, err);
     return rc;

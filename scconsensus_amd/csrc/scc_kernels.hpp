@@ -303,3 +303,30 @@ hipError_t scc_launch_hc_chain(double* D, int N, scc_hc_state* S, int* chain, do
 hipError_t scc_launch_hc_gather_core(const void* P, int f32, int N, const int* core, int cs, double* block,
                                      hipStream_t st);
 }
+
+// ---- hclust from the scores (scc_hclust_vec.hip) -----------------------------
+// The centroid NN-chain's state between two launches (device memory): the
+// scalars of scc_hc_state, then what one scan hands to the next.
+struct scc_wv_state {
+    int start;  // lowest active node
+    int tip;    // chain length
+    int step;   // merges done
+    int err;    // SCC_HC_ERR_*: every later launch returns at once
+    long long scans;  // nearest-neighbour scans so far
+    int node;   // the node the next scan reads
+    int mode;   // 0: that scan restarts the chain from `start`; 1: it extends the chain
+    int i1;     // the node before the tip (the carried nearest neighbour)
+    int ext;    // scans of this chain extension
+    double mn;  // the carried minimum
+};
+extern "C" {
+int scc_wv_scan_workgroups(int N);  // partials of one scan
+hipError_t scc_launch_wv_init(const double* P, int N, double* C, scc_wv_state* S, double* size, uint8_t* act,
+                              unsigned int* nonfinite, hipStream_t st);
+hipError_t scc_launch_wv_scan(const double* C, int N, const scc_wv_state* S, const double* size, const uint8_t* act,
+                              double* part_v, int* part_i, hipStream_t st);
+hipError_t scc_launch_wv_advance(double* C, int N, scc_wv_state* S, int* chain, double* size, uint8_t* act,
+                                 const double* part_v, const int* part_i, int* out_a, int* out_b, double* out_h,
+                                 hipStream_t st);
+hipError_t scc_launch_wv_gather_core(const double* P, int N, const int* core, int cs, double* block, hipStream_t st);
+}
