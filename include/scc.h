@@ -440,6 +440,21 @@ SCC_API int scc_hclust_ward_d2_scores(scc_ctx* ctx, int64_t n, const void* score
 SCC_API int scc_cutree_hybrid_scores(scc_ctx* ctx, const int32_t* merge, const double* height, int64_t n,
                                      const void* scores, int32_t deep_split, int32_t min_cluster_size,
                                      int32_t* labels, double* cut_height);
+/* scc_silhouette of dist(scores) without the packed vector: deepSplitInfo's SI (Fast:433)
+ * on this route.  Each d(i, j) is computed from score rows i and j with the dist kernel's
+ * arithmetic where scc_silhouette loads it, and summed in the same order, so widths and
+ * clus_avg are bit for bit those of scc_silhouette on the f64 scc_distance_scores output of
+ * the same scores.  Device memory: the scores, 8 n n_groups doubles of partial sums, O(n)
+ * besides.  groups, widths, clus_avg, n_groups: as scc_silhouette (sorted group ids,
+ * 2 <= n_groups < n_cells, singleton width 0, any output may be NULL).  scores: as
+ * scc_hclust_ward_d2_scores (read only; NULL = the kept scores).  SCC_ERR_NONFINITE: a
+ * non-finite score (counted on the device before the widths are read, never returned as NaN
+ * widths); SCC_ERR_INVALID: a bad group count, no kept scores, or scores of another size.
+ * More than 64 groups run as further passes that compute the entries again.  Runs on
+ * devices[0] only (timer family "silhouette_scores", one entry per call). */
+SCC_API int scc_silhouette_scores(scc_ctx* ctx, int64_t n_cells, const int32_t* groups /* host [N] */,
+                                  const void* scores /* device [n][16], NULL = kept */, double* widths,
+                                  double* clus_avg, int32_t* n_groups);
 
 /* ---- diagnostics (tests): the PCA eigensolver's parts on device pointers --
  * Not on the R path.  Each synchronises the device and returns 0 on success.

@@ -120,8 +120,12 @@
 # engine routes whenever no two candidate dissimilarities lie within rounding
 # of each other; on exact ties (duplicate cells) a valid Ward tree that may
 # resolve the tie differently.  deepSplitInfo's SI (Fast:433, computed and
-# discarded by the reference) is not computed: this route makes no C_scc_si
-# call; Fast:433's stop for fewer than 2 groups is kept.
+# discarded by the reference) is computed only with
+# options(scConsensus.engineScoresSI = TRUE): the engine's silhouette from the
+# scores (C_scc_si_scores: dist(scores) entry by entry, no N x N matrix; the SI
+# of the other routes, bit for bit, for equal groups).  Without the option the
+# route makes no silhouette call; Fast:433's stop for fewer than 2 groups is
+# kept either way.
 .scc_tree_from_scores <- function() identical(getOption("scConsensus.engineTree", FALSE), "scores")
 
 .scc_tree_and_colors_scores <- function(h, genes, n_cells, deepSplitValues, minClusterSize, with_si) {
@@ -137,6 +141,8 @@
     # silhouette() of fewer than 2 (or of n) groups is NA and Fast:433 stops on it
     k <- length(unique(grp))
     if (with_si && (k < 2L || k >= n_cells)) stop("$ operator is invalid for atomic vectors")
+    if (with_si && isTRUE(getOption("scConsensus.engineScoresSI", FALSE)))
+      invisible(.Call("C_scc_si_scores", as.integer(grp)))
   }
   names(colors) <- paste("deepsplit:", deepSplitValues)
   list(tree = tree, colors = colors)

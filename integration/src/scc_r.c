@@ -29,6 +29,8 @@
  *                   options(scConsensus.engineTree = "scores"): the engine stops
  *                   after the PCA (Fast:398-399) and keeps the scores; the tree
  *                   and the cuts are computed from them, no distance exists
+ *   C_scc_si_scores C_scc_si on that route, from the engine-kept scores
+ *                   (options(scConsensus.engineScoresSI = TRUE))
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -275,6 +277,28 @@ SEXP C_scc_si(SEXP groups)
     return Rf_ScalarReal(s / ng);
 }
 
+/* C_scc_si for options(scConsensus.engineTree = "scores"): the same mean, the
+ * silhouette computed from the engine-kept scores of the last C_scc_pca_scores
+ * call (scc_silhouette_scores: d = dist(scores) entry by entry, no N x N
+ * matrix; the SI of C_scc_si on the f64 distance of the same scores, bit for
+ * bit).  The same stop for fewer than 2 groups or as many groups as cells. */
+SEXP C_scc_si_scores(SEXP groups)
+{
+    ensure_ctx();
+    const int N = LENGTH(groups);
+    int32_t* g = (int32_t*)R_alloc((size_t)N, sizeof(int32_t));
+    for (int k = 0; k < N; ++k) g[k] = INTEGER(groups)[k];
+    double* avg = (double*)R_alloc((size_t)N, sizeof(double));
+    int32_t ng = 0;
+    int rc = scc_silhouette_scores(g_ctx, N, g, NULL, NULL, avg, &ng);
+    if (rc == SCC_ERR_INVALID && ng > 0 && (ng < 2 || ng >= N))
+        Rf_error("$ operator is invalid for atomic vectors");
+    check(rc);
+    double s = 0.0;
+    for (int k = 0; k < ng; ++k) s += avg[k];
+    return Rf_ScalarReal(s / ng);
+}
+
 /* n from the length of a "dist" body, n (n - 1) / 2 */
 static int64_t dist_n(SEXP d)
 {
@@ -453,6 +477,7 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_pca_scores", (DL_FUNC)&C_scc_pca_scores, 3},
     {"C_scc_hclust_scores", (DL_FUNC)&C_scc_hclust_scores, 1},
     {"C_scc_cutree_scores", (DL_FUNC)&C_scc_cutree_scores, 4},
+    {"C_scc_si_scores", (DL_FUNC)&C_scc_si_scores, 1},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

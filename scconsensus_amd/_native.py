@@ -49,7 +49,7 @@ EXPORTS = [
     "scc_distance", "scc_de_distance", "scc_distance_cols", "scc_pca_shard_colsum", "scc_pca_shard_gram", "scc_pca_shard_scores", "scc_pca_shard_eigen", "scc_pca_shard_project",
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
-    "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores",
+    "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_hclust_last_scans",
     "scc_diag_small_syev_stamps", "scc_diag_pvalues",
@@ -149,6 +149,7 @@ def load():
         "scc_pca_scores": (ctypes.c_int, [vp, vp, vp, i32, i32]),
         "scc_hclust_ward_d2_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp]),
         "scc_cutree_hybrid_scores": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
+        "scc_silhouette_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(i32)]),
         "scc_diag_hclust_last_scans": (i64, [vp]),
         "scc_diag_eigen_topk": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, P(ctypes.c_int)]),
         "scc_diag_small_syev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp]),
@@ -643,6 +644,22 @@ class Engine:
                                                       ctypes.c_void_p(scores_device_ptr or None), int(deep_split),
                                                       int(min_cluster_size), _ptr(lab), ctypes.byref(cut)))
         return lab, cut.value
+
+    def silhouette_scores(self, N, groups, scores_device_ptr=None):
+        """silhouette() for d = dist(scores) of a device [N][16] score matrix
+        (same rule as hclust_ward_d2_scores), without the N x N matrix:
+        (widths, per-cluster average widths), bit for bit what silhouette()
+        returns on the f64 distance of the same scores."""
+        N = int(N)
+        groups = np.ascontiguousarray(groups, np.int32)
+        if groups.shape != (N,):
+            raise ValueError("groups must hold one id per cell")
+        C = len(np.unique(groups))
+        w, ca, k = np.zeros(N), np.zeros(max(C, 1)), ctypes.c_int32()
+        self._check(self.lib.scc_silhouette_scores(self.ctx, N, _ptr(groups),
+                                                   ctypes.c_void_p(scores_device_ptr or None), _ptr(w), _ptr(ca),
+                                                   ctypes.byref(k)))
+        return w, ca[:k.value]
 
     def hclust_last_scans(self):
         """Nearest-neighbour scans of the last hclust_ward_d2_dev or hclust_ward_d2_scores (diagnostics)."""

@@ -175,7 +175,7 @@ def _distance_and_tree(eng, ds, uni, N, tree):
 
 
 def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None, info=None, cut_eng=None,
-                    scores_eng=None):
+                    scores_eng=None, scores_si=False):
     """Fast:418-431: cutreeDynamic(dendro, distM = as.matrix(d), deepSplit = dsv,
     pamStage = FALSE, minClusterSize) -> labels2colors, named "deepsplit: dsv".
     With ``eng`` (FAST, which computes the silhouette for every deepSplit):
@@ -186,8 +186,9 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
     silhouette computed by the engine on its HBM-resident copy of d.
     With ``cut_eng`` the cut reads that HBM-resident copy too (dist_packed is
     not used).  With ``scores_eng`` there is no distance: the cut computes its
-    distM entries from the engine-kept scores and the rows' SI is None (the
-    silhouette from the scores is not part of this route)."""
+    distM entries from the engine-kept scores; the rows' SI is None unless
+    ``scores_si``, which computes it from the scores too (silhouette_scores:
+    the SI of the matrix routes, bit for bit, for equal labels)."""
     out = {}
     N = len(tree["order"])
     for dsv in deepSplitValues:
@@ -206,7 +207,10 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
                 raise RuntimeError("$ operator is invalid for atomic vectors (silhouette of "
                                    f"{k} group(s) at deepSplit {dsv}, Fast:433)")
             if info is not None:  # the SI the reference computes and discards
-                si = None if scores_eng is not None else float(np.mean(eng.silhouette(N, lab)[1]))
+                if scores_eng is None:
+                    si = float(np.mean(eng.silhouette(N, lab)[1]))
+                else:
+                    si = float(np.mean(scores_eng.silhouette_scores(N, lab)[1])) if scores_si else None
                 info.append({"DeepSplit": dsv, "NumbersOfClusters": k, "SI": si})
     return out
 
@@ -223,8 +227,10 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
                              deepSplitValues=(1, 2, 3, 4), minClusterSize=10, minPerCent=20,
                              filename="de_gene_object.rds", plotName="DE_Heatmap", NumbertopDEGenes=30, nCores=1,
                              *, gene_names=None, cluster_order=None, device=0, save=False, return_details=False,
-                             tree="host"):
+                             tree="host", scores_si=False):
     on_device = _check_tree(tree)
+    if scores_si and tree != "scores":
+        raise ValueError('scores_si=True needs tree="scores" (the other routes compute SI from the distance)')
     if method not in ("wilcox", "t", "bimod"):
         # Fast:306-333: "roc" yields no p_val_adj, which the caller filters on (Fast:343-351,377)
         raise NotImplementedError(f"Unknown test: {method} (this engine implements test.use = 'wilcox', 't' "
@@ -249,13 +255,14 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
     if len(uni) == 0:
         raise RuntimeError("no DE genes (R fails on an empty deGenes data frame, Fast:386)")
     # tree="device": the distance stays in the engine (d is None), the tree, the cuts and the silhouette read it there;
-    # tree="scores": no distance, the tree and the cuts read the engine-kept scores
+    # tree="scores": no distance, the tree and the cuts (and with scores_si the silhouette) read the engine-kept scores
     d, cell_tree = _distance_and_tree(eng, ds, uni, N, tree)
     info = [] if return_details else None  # deepSplitInfo: computed by the reference, never returned (Fast:433)
     ret = {"deGeneUnion": list(gnames[uni]), "cellTree": cell_tree,
            "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize, eng, info,
                                             cut_eng=eng if on_device else None,
-                                            scores_eng=eng if tree == "scores" else None)}
+                                            scores_eng=eng if tree == "scores" else None,
+                                            scores_si=bool(scores_si))}
     if save:
         _save(ret, filename)
     if return_details:

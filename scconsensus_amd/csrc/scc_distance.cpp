@@ -37,6 +37,8 @@ hipError_t scc_launch_scores(const double* Xc, int N, int nu, int ld, const doub
 size_t scc_sil_scratch_doubles(int N, int C);
 hipError_t scc_launch_silhouette(const void* D, int f32, int N, const int* lab, const int* cnt, int C, double* part,
                                  double* width, hipStream_t st);
+hipError_t scc_launch_silhouette_scores(const double* P, int N, const int* lab, const int* cnt, int C, double* part,
+                                        double* width, unsigned int* nonfinite, hipStream_t st);
 hipError_t scc_launch_dist_euclid(const double* P, int N, int c_lo, int c_hi, void* out, int f32, hipStream_t st);
 hipError_t scc_launch_zscore(const double* Xc, int N, int nu, int ld, float* Z, int ldz, hipStream_t st);
 hipError_t scc_launch_pearson(const double* Xc, int N, int nu, int ld, float* Z, int ldz, int c_lo, int c_hi,
@@ -804,18 +806,11 @@ static int kept_dist(scc_ctx* c, int64_t N, const char* who, const void** D, int
     return SCC_OK;
 }
 
-extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups, const void* dist, int32_t dist_f32,
-                              double* widths, double* clus_avg, int32_t* n_groups)
+// Both silhouettes after their source is settled: the packed vector D (f64 or
+// f32), or, when P is set, the [N][16] scores whose dist() it would be.
+static int silhouette_run(scc_ctx* c, int N, const int32_t* groups, const void* D, int f32, const double* P,
+                          bool kept_d, double* widths, double* clus_avg, int32_t* n_groups)
 {
-    if (!c || !groups) return fail(c, SCC_ERR_INVALID, "scc_silhouette: null argument");
-    const int N = (int)n_cells;
-    if (N < 2) return fail(c, SCC_ERR_INVALID, "scc_silhouette: need at least two cells");
-    const void* D = dist;
-    int f32 = dist_f32 ? 1 : 0;
-    if (!D) {
-        int rck = kept_dist(c, N, "scc_silhouette", &D, &f32);
-        if (rck) return rck;
-    }
     // cluster codes in increasing id order (silhouette's sorted clusters)
     std::vector<int32_t> ids(groups, groups + N);
     std::sort(ids.begin(), ids.end());
@@ -833,22 +828,31 @@ extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups
     int rc;
     int *d_lab, *d_cnt;
     double *d_part, *d_w;
+    unsigned int* d_bad = nullptr;
     if ((rc = ws(c, "sil_lab", N, &d_lab))) return rc;
     if ((rc = ws(c, "sil_cnt", C, &d_cnt))) return rc;
     if ((rc = ws(c, "sil_part", scc_sil_scratch_doubles(N, C), &d_part))) return rc;
     if ((rc = ws(c, "sil_w", N, &d_w))) return rc;
+    if (P && (rc = ws(c, "sil_bad", 1, &d_bad))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_lab, lab.data(), sizeof(int) * N, hipMemcpyHostToDevice, s0));
     HIPCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int) * C, hipMemcpyHostToDevice, s0));
-    {
+    if (P) {
+        Scope sc(c, "silhouette_scores", s0);
+        HIPCHK(c, scc_launch_silhouette_scores(P, N, d_lab, d_cnt, C, d_part, d_w, d_bad, s0));
+    } else {
         Scope sc(c, "silhouette", s0);
         HIPCHK(c, scc_launch_silhouette(D, f32, N, d_lab, d_cnt, C, d_part, d_w, s0));
     }
     std::vector<double> w(N);
+    unsigned int bad = 0;
+    if (P) HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s0));
     HIPCHK(c, hipMemcpyAsync(w.data(), d_w, sizeof(double) * N, hipMemcpyDeviceToHost, s0));
     HIPCHK(c, hipStreamSynchronize(s0));
+    // the count of k_sil_nonfinite, not the widths, says whether they are an answer
+    if (bad) return fail(c, SCC_ERR_NONFINITE, "scc_silhouette_scores: the scores hold a non-finite entry");
     // widths read from an engine-kept distance whose eigensolve failed are
     // not an answer: report the flag that distance left (and drop it)
-    if (!dist && (rc = check_pending_eig(c))) {
+    if (kept_d && (rc = check_pending_eig(c))) {
         c->d_last_dist = nullptr;
         return rc;
     }
@@ -859,6 +863,21 @@ extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups
         for (int k = 0; k < C; ++k) clus_avg[k] = (double)(sum[k] / cnt[k]);
     }
     return SCC_OK;
+}
+
+extern "C" int scc_silhouette(scc_ctx* c, int64_t n_cells, const int32_t* groups, const void* dist, int32_t dist_f32,
+                              double* widths, double* clus_avg, int32_t* n_groups)
+{
+    if (!c || !groups) return fail(c, SCC_ERR_INVALID, "scc_silhouette: null argument");
+    const int N = (int)n_cells;
+    if (N < 2) return fail(c, SCC_ERR_INVALID, "scc_silhouette: need at least two cells");
+    const void* D = dist;
+    int f32 = dist_f32 ? 1 : 0;
+    if (!D) {
+        int rck = kept_dist(c, N, "scc_silhouette", &D, &f32);
+        if (rck) return rck;
+    }
+    return silhouette_run(c, N, groups, D, f32, nullptr, !dist, widths, clus_avg, n_groups);
 }
 
 // ---- hclust(ward.D2) and the tree cut on the device-resident distance ------
@@ -1188,6 +1207,20 @@ extern "C" int scc_cutree_hybrid_scores(scc_ctx* c, const int32_t* merge, const 
     }
     if (rc != SCC_OK && !err.empty()) return fail(c, rc, err);
     return rc;
+}
+
+extern "C" int scc_silhouette_scores(scc_ctx* c, int64_t n_cells, const int32_t* groups, const void* scores,
+                                     double* widths, double* clus_avg, int32_t* n_groups)
+{
+    if (!c || !groups) return fail(c, SCC_ERR_INVALID, "scc_silhouette_scores: null argument");
+    if (n_cells < 2 || n_cells > (int64_t)INT32_MAX)
+        return fail(c, SCC_ERR_INVALID, "scc_silhouette_scores: bad cell count");
+    const int N = (int)n_cells;
+    scc_enter(c);
+    const double* P = (const double*)scores;
+    int rc;
+    if (!P && (rc = kept_scores(c, N, "scc_silhouette_scores", &P))) return rc;
+    return silhouette_run(c, N, groups, nullptr, 0, P, false, widths, clus_avg, n_groups);
 }
 
 extern "C" int scc_last_pca_scores(const scc_ctx* c, double* scores, int32_t* ncomp)

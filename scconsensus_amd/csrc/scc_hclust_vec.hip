@@ -49,6 +49,7 @@
 //               values the packed vector would hold, bit for bit.
 #include "scc.h"
 #include "scc_common.hpp"
+#include "scc_dist_entry.hpp"
 #include "scc_kernels.hpp"
 
 #define WV_THREADS 256
@@ -318,8 +319,7 @@ __global__ void __launch_bounds__(WV_THREADS) k_wv_advance(double* C, int N, scc
 }
 
 // One entry of the packed vector as k_dist_aligned forms it (row i > column
-// j): the fma chains over the 15 components, fma(-2, dot, ni + nj), the
-// difference form below 2^-20 of the norm sum, scc_sqrt_nr.
+// j), from the two score rows (scc_dist_entry.hpp).
 __device__ inline double wv_dist_entry(const double* __restrict__ P, int i, int j)
 {
     double pi[15], pj[15];
@@ -328,24 +328,7 @@ __device__ inline double wv_dist_entry(const double* __restrict__ P, int i, int 
         pi[q] = P[(size_t)i * 16 + q];
         pj[q] = P[(size_t)j * 16 + q];
     }
-    double ni = 0.0, nj = 0.0, dot = 0.0;
-#pragma unroll
-    for (int q = 0; q < 15; ++q) ni = fma(pi[q], pi[q], ni);
-#pragma unroll
-    for (int q = 0; q < 15; ++q) nj = fma(pj[q], pj[q], nj);
-#pragma unroll
-    for (int q = 0; q < 15; ++q) dot = fma(pi[q], pj[q], dot);
-    const double nsum = ni + nj;
-    double s = fma(-2.0, dot, nsum);
-    if (s < 0x1p-20 * nsum) {  // near-identical cells: the difference form
-        s = 0.0;
-#pragma unroll
-        for (int q = 0; q < 15; ++q) {
-            const double dv = pi[q] - pj[q];
-            s = fma(dv, dv, s);
-        }
-    }
-    return scc_sqrt_nr(s);
+    return scc_dist_entry15(pi, scc_dist_norm15(pi), pj, scc_dist_norm15(pj));
 }
 
 // block[j * cs + i] = distM[core[i], core[j]] (core: 1-based ids; 0 on the diagonal)
