@@ -11,6 +11,8 @@
  *       prcomp_irlba + dist                         :398-400 -> scc_distance(SCC_DIST_PCA_EUCLID)
  *       `1 - cor(...)` (commented alternative)      :403     -> scc_distance(SCC_DIST_PEARSON)
  *       nodg loop                                   :440-443 -> scc_de_result_nodg
+ *       cellTypeDEPlot's Heatmap inputs             :456-464 -> scc_gene_distance, scc_hclust_complete,
+ *                                                               scc_dendro_reorder, scc_heatmap_raster
  *   reclusterDEConsensus()      R/reclusterDEConsensus.R:20-29
  *       global threshold + pair loop + union        :32-227  -> scc_de_run(SCC_DE_SLOW)
  *       prcomp_irlba + dist                         :234-236 -> scc_distance(SCC_DIST_PCA_EUCLID)
@@ -455,6 +457,76 @@ SCC_API int scc_cutree_hybrid_scores(scc_ctx* ctx, const int32_t* merge, const d
 SCC_API int scc_silhouette_scores(scc_ctx* ctx, int64_t n_cells, const int32_t* groups /* host [N] */,
                                   const void* scores /* device [n][16], NULL = kept */, double* widths,
                                   double* clus_avg, int32_t* n_groups);
+
+/* ---- heatmap inputs (cellTypeDEPlot.R:168-253) ---------------------------
+ * What both reference functions end with (Fast:456-464, slow:288-296):
+ * cellTypeDEPlot(dataMatrix[deGeneUnion, ], ...) hands the |U| x N block to
+ * ComplexHeatmap::Heatmap(cluster_rows = TRUE, use_raster = TRUE), which
+ * clusters the GENE rows (dist, hclust "complete", a dendrogram reorder by
+ * -rowMeans) and rasterises every cell; the colour ramp needs the extrema of x
+ * and |x| (cellTypeDEPlot.R:174-222).  These four calls compute those inputs;
+ * the drawing stays with the caller.  The two device calls run on devices[0]
+ * only; their host outputs may each be NULL.
+ *
+ * scc_gene_distance: dist = dist(X[U, ], "euclidean"), the genes as
+ * observations over ALL n_cells cells, packed in R `dist` order (nu (nu-1)/2
+ * doubles).  Each entry is sqrt(sum_c (x_ac - x_bc)^2) from the direct
+ * differences (no Gram identity: no cancellation, identical rows give exactly
+ * 0.0), the cells split into slabs whose partial sums are added in a fixed
+ * order: two calls return the same bits, and within 2 N 2^-53 relative of the
+ * exact value.  row_mean[u] = rowMeans(X[U, ])[u], from the double-double
+ * column sums the PCA's centring uses.  range = {min x, max x, min |x|,
+ * max |x|} over the nu x N block, a sparse dataset's implicit zeros included
+ * (elements of the input, exact).
+ *   SCC_ERR_INVALID    nu < 2, a gene out of range or listed twice, a dataset
+ *                      of another context
+ *   SCC_ERR_NONFINITE  a non-finite value in the block (counted on the device
+ *                      before any output is copied; no NaN distance is returned)
+ *   SCC_ERR_OOM        the [N][ld] panel (ld = nu rounded up to 64) plus the
+ *                      slabs do not fit in half of the free device memory (the
+ *                      rule of scc_hclust_ward_d2_dev)
+ * Both device calls work in workspace buffers of their own ("hm_*"): the
+ * engine-kept distance and scores of an earlier scc_distance / scc_pca_scores,
+ * and the PCA's panel, are left as they were (a later NULL-distance
+ * scc_silhouette returns what it returned before).  Timer family "gene_dist"
+ * (one entry per call: the pair kernel and the slab reduction). */
+SCC_API int scc_gene_distance(scc_ctx* ctx, const scc_dataset* ds, const int32_t* genes /* host [nu] */, int32_t nu,
+                              double* dist /* host [nu (nu-1)/2] */, double* row_mean /* host [nu] */,
+                              double* range /* host [4] */);
+/* stats::hclust(d, "complete") on a host packed `dist` vector (host code, no
+ * device): merge, height, order as scc_hclust_ward_d2.  Heights are entries of
+ * dist, unmodified.  An O(n^2) NN-chain (complete linkage is reducible); on
+ * exact ties the lowest index wins, and the result is then a valid
+ * complete-linkage tree that R (which merges the globally closest pair at
+ * every step) may resolve otherwise.  SCC_ERR_NONFINITE: a non-finite entry. */
+SCC_API int scc_hclust_complete(const double* dist, int64_t n, int32_t* merge, double* height, int32_t* order);
+/* stats::reorder.dendrogram(as.dendrogram(tree), wts, agglo.FUN = mean) (host
+ * code): a leaf's value is wts[leaf], an inner node's the mean of its two
+ * children's values (R's mean(): long-double sum, one correction pass);
+ * children are placed in increasing value, an equal pair keeps its order.
+ * merge: column-major (n-1) x 2 as hclust returns it; merge_out: the same
+ * with the two entries of a row swapped where the children swap (it no longer
+ * obeys hclust's singletons-first rule, which as.dendrogram does not need);
+ * order_out [n]: the resulting 1-based leaf order.  Either output may be NULL.
+ * ComplexHeatmap's default row weight is -rowMeans(mat).  SCC_ERR_INVALID: a
+ * merge matrix that is not a tree over n leaves. */
+SCC_API int scc_dendro_reorder(const int32_t* merge, int64_t n, const double* wts /* [n] */, int32_t* merge_out,
+                               int32_t* order_out);
+/* The raster ComplexHeatmap draws with use_raster = TRUE, reduced to `width`
+ * columns: out row r is gene genes[row_order[r] - 1]; out column b is the
+ * mean of that gene over the cells cell_order[floor(b N / width) ..
+ * floor((b + 1) N / width)), summed in cell_order order and divided once.
+ * 1 <= width <= N; with width == N the output is the reordered matrix itself,
+ * bit for bit.  row_order: 1-based positions into genes (a permutation of
+ * 1..nu); cell_order: 1-based cells (a permutation of 1..N, an hclust $order).
+ * out: host f64 [nu][width], row-major.  nu >= 1.  SCC_ERR_INVALID: an order
+ * that is not a permutation, a bad width, a gene out of range or listed
+ * twice; SCC_ERR_OOM as scc_gene_distance (the panel plus the [width][ld]
+ * device raster).  Workspace: as scc_gene_distance.  Timer family
+ * "heatmap_raster". */
+SCC_API int scc_heatmap_raster(scc_ctx* ctx, const scc_dataset* ds, const int32_t* genes /* host [nu] */, int32_t nu,
+                               const int32_t* row_order /* host [nu] */, const int32_t* cell_order /* host [N] */,
+                               int32_t width, double* out /* host [nu][width] */);
 
 /* ---- diagnostics (tests): the PCA eigensolver's parts on device pointers --
  * Not on the R path.  Each synchronises the device and returns 0 on success.

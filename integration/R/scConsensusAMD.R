@@ -6,7 +6,8 @@
 #   reclusterDEConsensus      R/reclusterDEConsensus.R:20-29,      returns :278-282
 # Kept in R (host), exactly as the reference does them: cluster selection
 # (table / grepl("grey") / locale order), hclust(ward.D2), cutreeDynamic,
-# labels2colors, silhouette, saveRDS, printing and cellTypeDEPlot.
+# labels2colors, silhouette, saveRDS, printing and cellTypeDEPlot (opt-in:
+# its gene-row tree from the engine, options(scConsensus.engineHeatmapRows)).
 
 # Cluster selection exactly as Fast:39-47 / slow:38-48: table() over ALL of
 # consensusClusterLabels (locale collation), "> minClusterSize", no "grey";
@@ -148,6 +149,86 @@
   list(tree = tree, colors = colors)
 }
 
+# ---- the heatmap's gene rows on the engine (opt-in) --------------------------
+# cellTypeDEPlot ends in ComplexHeatmap::Heatmap(cluster_rows = TRUE), which
+# runs dist() over the |U| gene rows (|U|^2 N / 2 subtract-multiply-adds on one
+# R thread), hclust("complete") and a reorder by -rowMeans.  sccHeatmapRows
+# computes the same row tree through the engine (C_scc_heatmap_rows: the
+# distance on the device, the tree and the reorder in libscc's host code) and
+# returns it as an "hclust" object, already reordered, with the colour ramp's
+# inputs attached:
+#   attr(, "range")    c(min x, max x, min |x|, max |x|) over dataMatrix[deGeneUnion, ]
+#   attr(, "rowMeans") rowMeans(dataMatrix[deGeneUnion, ])
+# dataset: the matrix (dgCMatrix, dgRMatrix or base matrix) or a handle of
+# .scc_dataset; deGeneUnion: row names or 1-based row indices.  On exact ties
+# the tree is a valid complete-linkage tree that stats::hclust may resolve
+# otherwise.  $merge is the reordered matrix (children in drawing order), so it
+# does not list singletons first; as.dendrogram does not need that.
+sccHeatmapRows <- function(dataset, deGeneUnion) {
+  own <- !inherits(dataset, "externalptr")
+  if (own && is.character(deGeneUnion)) {
+    rows <- match(deGeneUnion, rownames(dataset))
+    labels <- deGeneUnion
+  } else {
+    rows <- as.integer(deGeneUnion)
+    labels <- if (own && !is.null(rownames(dataset))) rownames(dataset)[rows] else NULL
+  }
+  if (anyNA(rows)) stop("sccHeatmapRows: a gene of deGeneUnion is not a row of the matrix")
+  h <- if (own) .scc_dataset(dataset) else dataset
+  if (own) on.exit(.Call("C_scc_release", h), add = TRUE)
+  t <- .Call("C_scc_heatmap_rows", h, as.integer(rows))
+  tree <- structure(list(merge = t[[1]], height = t[[2]], order = t[[3]], labels = labels,
+                         method = "complete", call = match.call(), dist.method = "euclidean"),
+                    class = "hclust")
+  attr(tree, "range") <- t[[4]]
+  attr(tree, "rowMeans") <- t[[5]]
+  tree
+}
+
+# The drawing for options(scConsensus.engineHeatmapRows = TRUE): the wrapper's
+# own plotting helper, written from ComplexHeatmap's documented arguments.  Rows
+# follow the engine's tree (cluster_rows = a dendrogram, row_dend_reorder =
+# FALSE: it is reordered already), columns follow cellTree as given, the ramp
+# runs over [min |x|, max |x|] from the engine's range, and the cells carry
+# their consensus label, one colour strip per deepSplit and a bar of nodg.
+.scc_heatmap_plot <- function(mat, rowTree, nodg, cellTree, clusterLabels, dynamicColorsList, filename) {
+  rng <- attr(rowTree, "range")
+  stops <- seq(rng[3], rng[4], length.out = 5)
+  ramp <- circlize::colorRamp2(stops, grDevices::colorRampPalette(c("slateblue1", "white", "red", "darkred"))(5))
+  strips <- as.data.frame(dynamicColorsList, check.names = FALSE, stringsAsFactors = FALSE)
+  stripCols <- lapply(strips, function(v) stats::setNames(unique(v), unique(v)))
+  strips[["consensus"]] <- as.character(clusterLabels[colnames(mat)])
+  top <- ComplexHeatmap::HeatmapAnnotation(
+    df = strips, col = stripCols,
+    NODG = ComplexHeatmap::anno_barplot(nodg),
+    which = "column", annotation_name_side = "left")
+  ht <- ComplexHeatmap::Heatmap(
+    matrix = as.matrix(mat), col = ramp, name = "expression",
+    cluster_rows = stats::as.dendrogram(rowTree), row_dend_reorder = FALSE,
+    cluster_columns = stats::as.dendrogram(cellTree), column_dend_reorder = FALSE,
+    top_annotation = top, show_column_names = FALSE,
+    row_names_gp = grid::gpar(fontsize = 5), use_raster = TRUE)
+  grDevices::pdf(paste0(filename, ".pdf"), width = 50, height = 50)
+  on.exit(grDevices::dev.off(), add = TRUE)
+  ComplexHeatmap::draw(ht)
+  invisible(ht)
+}
+
+# the last step of both functions: the reference's cellTypeDEPlot (default), or
+# with options(scConsensus.engineHeatmapRows = TRUE) the helper above on the
+# engine's row tree
+.scc_plot <- function(h, mat, genes, nodg, cellTree, clusterLabels, dynamicColorsList, plotName) {
+  if (isTRUE(getOption("scConsensus.engineHeatmapRows", FALSE)) && length(genes) >= 2L) {
+    rowTree <- sccHeatmapRows(h, genes)
+    rowTree$labels <- rownames(mat)
+    .scc_heatmap_plot(mat, rowTree, nodg, cellTree, clusterLabels, dynamicColorsList, plotName)
+  } else {
+    cellTypeDEPlot(dataMatrix = mat, nodg = nodg, cellTree = cellTree,
+                   clusterLabels = clusterLabels, dynamicColorsList = dynamicColorsList,
+                   colScheme = "violet", filename = plotName)
+  }
+}
+
 reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method = "wilcox",
                                      qValThrs = 0.1, logFCThrs = 0.5, deepSplitValues = 1:4,
                                      minClusterSize = 10, minPerCent = 20,
@@ -177,9 +258,7 @@ reclusterDEConsensusFast <- function(dataMatrix, consensusClusterLabels, method 
   }
   out <- list("deGeneUnion" = deGeneUnion, "cellTree" = tc$tree, "dynamicColors" = tc$colors)
   saveRDS(object = out, file = filename)
-  cellTypeDEPlot(dataMatrix = dataMatrix[deGeneUnion, ], nodg = res[[2]], cellTree = tc$tree,
-                 clusterLabels = consensusClusterLabels, dynamicColorsList = tc$colors,
-                 colScheme = "violet", filename = plotName)
+  .scc_plot(h, dataMatrix[deGeneUnion, ], res[[1]], res[[2]], tc$tree, consensusClusterLabels, tc$colors, plotName)
   out
 }
 
@@ -224,8 +303,7 @@ reclusterDEConsensus <- function(dataMatrix, consensusClusterLabels, method = "W
   }
   out <- list("deGeneUnion" = deGeneUnion, "cellTree" = tc$tree, "dynamicColors" = tc$colors)
   saveRDS(object = out, file = filename)
-  cellTypeDEPlot(dataMatrix = as.matrix(dataMatrix)[deGeneUnion, ], nodg = res[[5]], cellTree = tc$tree,
-                 clusterLabels = consensusClusterLabels, dynamicColorsList = tc$colors,
-                 colScheme = "violet", filename = plotName)
+  .scc_plot(h, as.matrix(dataMatrix)[deGeneUnion, ], res[[1]], res[[5]], tc$tree, consensusClusterLabels, tc$colors,
+            plotName)
   out
 }

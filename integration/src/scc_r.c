@@ -461,7 +461,54 @@ SEXP C_scc_cutree_scores(SEXP merge, SEXP height, SEXP deep, SEXP minsize)
     return lab;
 }
 
+/* The heatmap's gene rows (cellTypeDEPlot.R:225-253: Heatmap(cluster_rows = TRUE)):
+ * dist() of the union's rows over all cells on the device (scc_gene_distance),
+ * hclust "complete" and ComplexHeatmap's reorder by -rowMeans on the host
+ * (scc_hclust_complete, scc_dendro_reorder).  Returns list(merge, height, order,
+ * range = c(min x, max x, min |x|, max |x|), rowMeans); merge is the reordered
+ * one (as.dendrogram takes it; it no longer lists singletons first). */
+SEXP C_scc_heatmap_rows(SEXP h, SEXP genes)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes);
+    if (nu < 2) Rf_error("scConsensus engine: the row tree needs at least two genes");
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int k = 0; k < nu; ++k) {
+        g0[k] = INTEGER(genes)[k] - 1;
+        if (g0[k] < 0 || g0[k] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[k] + 1);
+    }
+    double* d = (double*)R_alloc((size_t)nu * (size_t)(nu - 1) / 2, sizeof(double));
+    double* w = (double*)R_alloc((size_t)nu, sizeof(double));
+    int32_t* m0 = (int32_t*)R_alloc(2 * (size_t)(nu - 1), sizeof(int32_t));
+    SEXP merge = PROTECT(Rf_allocMatrix(INTSXP, nu - 1, 2));
+    SEXP height = PROTECT(Rf_allocVector(REALSXP, nu - 1));
+    SEXP order = PROTECT(Rf_allocVector(INTSXP, nu));
+    SEXP range = PROTECT(Rf_allocVector(REALSXP, 4));
+    SEXP means = PROTECT(Rf_allocVector(REALSXP, nu));
+    int rc = scc_gene_distance(g_ctx, ds, g0, nu, d, REAL(means), REAL(range));
+    if (rc == SCC_OK) rc = scc_hclust_complete(d, nu, m0, REAL(height), NULL);
+    if (rc == SCC_OK) {
+        for (int k = 0; k < nu; ++k) w[k] = -REAL(means)[k];
+        rc = scc_dendro_reorder(m0, nu, w, INTEGER(merge), INTEGER(order));
+    }
+    if (rc != SCC_OK) {
+        UNPROTECT(5);
+        check(rc);
+    }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 5));
+    SET_VECTOR_ELT(out, 0, merge);
+    SET_VECTOR_ELT(out, 1, height);
+    SET_VECTOR_ELT(out, 2, order);
+    SET_VECTOR_ELT(out, 3, range);
+    SET_VECTOR_ELT(out, 4, means);
+    UNPROTECT(6);
+    return out;
+}
+
 static const R_CallMethodDef call_methods[] = {
+    {"C_scc_heatmap_rows", (DL_FUNC)&C_scc_heatmap_rows, 2},
     {"C_scc_dataset", (DL_FUNC)&C_scc_dataset, 4},
     {"C_scc_release", (DL_FUNC)&C_scc_release, 1},
     {"C_scc_de_fast", (DL_FUNC)&C_scc_de_fast, 8},

@@ -50,6 +50,7 @@ EXPORTS = [
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
     "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
+    "scc_gene_distance", "scc_hclust_complete", "scc_dendro_reorder", "scc_heatmap_raster",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_hclust_last_scans",
     "scc_diag_small_syev_stamps", "scc_diag_pvalues",
@@ -150,6 +151,10 @@ def load():
         "scc_hclust_ward_d2_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp]),
         "scc_cutree_hybrid_scores": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
         "scc_silhouette_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(i32)]),
+        "scc_gene_distance": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, vp]),
+        "scc_hclust_complete": (ctypes.c_int, [vp, i64, vp, vp, vp]),
+        "scc_dendro_reorder": (ctypes.c_int, [vp, i64, vp, vp, vp]),
+        "scc_heatmap_raster": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, i32, vp]),
         "scc_diag_hclust_last_scans": (i64, [vp]),
         "scc_diag_eigen_topk": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, P(ctypes.c_int)]),
         "scc_diag_small_syev": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp]),
@@ -661,6 +666,33 @@ class Engine:
                                                    ctypes.byref(k)))
         return w, ca[:k.value]
 
+    # -------------------------------------------------------------- heatmap inputs
+    def gene_distance(self, ds: Dataset, genes):
+        """dist(X[genes, ], "euclidean") with the genes as observations over
+        all cells (packed R `dist` order), rowMeans and {min x, max x,
+        min |x|, max |x|} of the block: (dist, row_mean, range)."""
+        genes = np.ascontiguousarray(genes, np.int32)
+        nu = len(genes)
+        d = np.empty(max(nu * (nu - 1) // 2, 1))
+        mean, rng = np.empty(max(nu, 1)), np.empty(4)
+        self._check(self.lib.scc_gene_distance(self.ctx, ds.handle, _ptr(genes), nu, _ptr(d), _ptr(mean), _ptr(rng)))
+        return d[: nu * (nu - 1) // 2], mean[:nu], rng
+
+    def heatmap_raster(self, ds: Dataset, genes, row_order, cell_order, width):
+        """The |genes| x width raster: row r is gene genes[row_order[r] - 1],
+        column b the mean over the cells cell_order[floor(b N / width) ..
+        floor((b + 1) N / width)) (both orders 1-based permutations)."""
+        genes = np.ascontiguousarray(genes, np.int32)
+        ro = np.ascontiguousarray(row_order, np.int32)
+        co = np.ascontiguousarray(cell_order, np.int32)
+        if ro.shape != (len(genes),) or co.shape != (ds.N,):
+            raise ValueError("row_order must hold one entry per gene and cell_order one per cell")
+        width = int(width)
+        out = np.empty((len(genes), max(width, 1)))
+        self._check(self.lib.scc_heatmap_raster(self.ctx, ds.handle, _ptr(genes), len(genes), _ptr(ro), _ptr(co),
+                                                width, _ptr(out)))
+        return out
+
     def hclust_last_scans(self):
         """Nearest-neighbour scans of the last hclust_ward_d2_dev or hclust_ward_d2_scores (diagnostics)."""
         return int(self.lib.scc_diag_hclust_last_scans(self.ctx))
@@ -765,3 +797,37 @@ def cutree_hybrid(merge, height, dist_packed, deep_split=1, min_cluster_size=20)
     if rc != SCC_OK:
         raise SccError(rc, "scc_cutree_hybrid failed (deepSplit must be 0..4)")
     return lab, cut.value
+
+
+
+def hclust_complete(dist_packed, n):
+    """stats::hclust(d, "complete") -> (merge, height, order) as
+    hclust_ward_d2; heights are entries of dist_packed.  On exact ties the
+    lowest index wins: a valid complete-linkage tree R may resolve otherwise."""
+    d = np.ascontiguousarray(dist_packed, np.float64)
+    if d.shape != (n * (n - 1) // 2,):
+        raise ValueError("dist_packed must hold n(n-1)/2 entries")
+    merge = np.zeros(2 * (n - 1), np.int32)
+    height = np.zeros(n - 1)
+    order = np.zeros(n, np.int32)
+    rc = load().scc_hclust_complete(_ptr(d), n, _ptr(merge), _ptr(height), _ptr(order))
+    if rc != SCC_OK:
+        raise SccError(rc, "scc_hclust_complete failed")
+    return merge.reshape(2, n - 1).T.copy(), height, order
+
+
+def dendro_reorder(merge, wts):
+    """stats::reorder.dendrogram(as.dendrogram(tree), wts, agglo.FUN = mean):
+    (merge with the swapped rows, the new 1-based leaf order)."""
+    merge = np.asarray(merge)
+    n = merge.shape[0] + 1
+    m = np.ascontiguousarray(merge.T.reshape(-1), np.int32)
+    w = np.ascontiguousarray(wts, np.float64)
+    if w.shape != (n,):
+        raise ValueError("wts must hold one weight per leaf")
+    mo = np.zeros(2 * (n - 1), np.int32)
+    order = np.zeros(n, np.int32)
+    rc = load().scc_dendro_reorder(_ptr(m), n, _ptr(w), _ptr(mo), _ptr(order))
+    if rc != SCC_OK:
+        raise SccError(rc, "scc_dendro_reorder failed (merge is not a tree over len(wts) leaves)")
+    return mo.reshape(2, n - 1).T.copy(), order

@@ -25,8 +25,13 @@ scores (scc_pca_scores / scc_hclust_ward_d2_scores / scc_cutree_hybrid_scores),
 for cell counts whose N x N matrix fits nowhere.  That route returns the same
 tree whenever no two candidate dissimilarities lie within rounding of each
 other; on exact ties (duplicate cells) it returns a valid Ward tree that may
-resolve the tie differently.  The ComplexHeatmap plot is not part of this
-engine; ``plotName`` is ignored.
+resolve the tie differently.  The ComplexHeatmap plot itself (PDF, colours,
+annotation bars) is not drawn here, but what it computes before drawing is:
+with ``heatmap=True`` (or an integer raster width) both functions add
+``ret["heatmap"]`` (see ``heatmap_data``: the gene-row tree of
+cellTypeDEPlot's ``cluster_rows = TRUE``, the row means, the colour ramp's
+extrema and the binned raster), and with ``save=True`` write it to
+``plotName + ".npz"``; ``plotName`` is otherwise unused.
 """
 from __future__ import annotations
 
@@ -215,6 +220,60 @@ def _dynamic_colors(tree, dist_packed, deepSplitValues, minClusterSize, eng=None
     return out
 
 
+def _heatmap(eng, ds, uni, cell_tree, width=None, row_reorder="-mean"):
+    """heatmap_data on an uploaded dataset (cellTypeDEPlot.R:168-253)."""
+    if row_reorder not in ("-mean", None):
+        raise ValueError(f"row_reorder must be '-mean' or None, not {row_reorder!r}")
+    uni = np.ascontiguousarray(uni, np.int32)
+    nu, N = len(uni), ds.N
+    col_order = np.asarray(cell_tree["order"], np.int32)
+    if width is None or width is True:
+        width = min(N, 4096)
+    d, means, rng = eng.gene_distance(ds, uni)
+    merge, height, order = nat.hclust_complete(d, nu)
+    if row_reorder == "-mean":  # ComplexHeatmap's default: reorder.dendrogram(, -rowMeans(mat), mean)
+        merge, order = nat.dendro_reorder(merge, -means)
+    raster = eng.heatmap_raster(ds, uni, order, col_order, int(width))
+    return {"rowTree": {"merge": merge, "height": height, "order": order, "method": "complete",
+                        "dist.method": "euclidean"},
+            "rowOrder": order, "colOrder": col_order, "rowMeans": means, "range": rng, "raster": raster}
+
+
+def heatmap_data(dataMatrix, union_idx, cellTree, width=None, row_reorder="-mean", device=0):
+    """What cellTypeDEPlot(dataMatrix[deGeneUnion, ], ...) computes before it
+    draws (ComplexHeatmap::Heatmap(cluster_rows = TRUE, use_raster = TRUE),
+    cellTypeDEPlot.R:168-253), on the engine: a dict with
+      rowTree   hclust(dist(X[U, ]), "complete") of the gene rows (merge,
+                height, order, method), reordered by ``row_reorder`` ("-mean":
+                reorder.dendrogram by -rowMeans with agglo.FUN = mean, the
+                ComplexHeatmap default; None: the tree as hclust returns it)
+      rowOrder  rowTree's 1-based leaf order (positions into union_idx)
+      colOrder  cellTree["order"]
+      rowMeans  rowMeans(X[U, ])
+      range     min x, max x, min |x|, max |x| over the block (the colour ramp)
+      raster    |U| x width bin means in (rowOrder, colOrder) order;
+                width=None: min(N, 4096)
+    union_idx: 0-based gene rows (at least two)."""
+    eng = _engine(device)
+    ds = _upload(eng, _as_matrix(dataMatrix))
+    try:
+        return _heatmap(eng, ds, union_idx, cellTree, width, row_reorder)
+    finally:
+        ds.close()
+
+
+def _heatmap_opt(eng, ds, uni, cell_tree, heatmap, save, plotName):
+    """The recluster* functions' ``heatmap`` keyword: False / True / a raster width."""
+    if heatmap is False or heatmap is None:
+        return None
+    hm = _heatmap(eng, ds, uni, cell_tree, None if heatmap is True else int(heatmap))
+    if save and plotName:
+        np.savez(plotName + ".npz", merge=hm["rowTree"]["merge"], height=hm["rowTree"]["height"],
+                 rowOrder=hm["rowOrder"], colOrder=hm["colOrder"], rowMeans=hm["rowMeans"], range=hm["range"],
+                 raster=hm["raster"])
+    return hm
+
+
 def _save(obj, filename):
     if not filename:
         return
@@ -227,7 +286,7 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
                              deepSplitValues=(1, 2, 3, 4), minClusterSize=10, minPerCent=20,
                              filename="de_gene_object.rds", plotName="DE_Heatmap", NumbertopDEGenes=30, nCores=1,
                              *, gene_names=None, cluster_order=None, device=0, save=False, return_details=False,
-                             tree="host", scores_si=False):
+                             tree="host", scores_si=False, heatmap=False):
     on_device = _check_tree(tree)
     if scores_si and tree != "scores":
         raise ValueError('scores_si=True needs tree="scores" (the other routes compute SI from the distance)')
@@ -263,6 +322,9 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
                                             cut_eng=eng if on_device else None,
                                             scores_eng=eng if tree == "scores" else None,
                                             scores_si=bool(scores_si))}
+    hm = _heatmap_opt(eng, ds, uni, cell_tree, heatmap, save, plotName)
+    if hm is not None:
+        ret["heatmap"] = hm
     if save:
         _save(ret, filename)
     if return_details:
@@ -275,7 +337,7 @@ def reclusterDEConsensusFast(dataMatrix, consensusClusterLabels, method="wilcox"
 def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", meanScalingFactor=5, qValThrs=None,
                          fcThrs=None, deepSplitValues=(1, 2, 3, 4), minClusterSize=10, filename="de_gene_object.rds",
                          plotName="DE_Heatmap", *, gene_names=None, cluster_order=None, device=0, save=False,
-                         return_details=False, tree="host"):
+                         return_details=False, tree="host", heatmap=False):
     on_device = _check_tree(tree)
     if qValThrs is None or fcThrs is None:
         raise TypeError('argument "qValThrs"/"fcThrs" is missing, with no default')
@@ -316,6 +378,9 @@ def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", 
            "dynamicColors": _dynamic_colors(cell_tree, d, deepSplitValues, minClusterSize,
                                             cut_eng=eng if on_device else None,
                                             scores_eng=eng if tree == "scores" else None)}
+    hm = _heatmap_opt(eng, ds, uni, cell_tree, heatmap, save, plotName)
+    if hm is not None:
+        ret["heatmap"] = hm
     if save:
         _save({"qValueList": qlist, "logFCList": lflist, "deGeneList": delist}, "de_lists")
         _save(ret, filename)

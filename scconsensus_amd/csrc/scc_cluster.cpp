@@ -8,6 +8,10 @@
 //   cutreeDynamic(dendro = cellTree, distM = as.matrix(d), deepSplit = dsv,
 //                 pamStage = FALSE, minClusterSize = minClusterSize)  Fast:421-427
 //   WGCNA::labels2colors(dynamicGroups)                       Fast:428
+// and, for the heatmap's gene rows (cellTypeDEPlot.R:225-253: ComplexHeatmap's
+// cluster_rows = TRUE), scc_hclust_complete and scc_dendro_reorder:
+//   stats::hclust(dist(mat), "complete")
+//   stats::reorder.dendrogram(as.dendrogram(.), -rowMeans(mat), agglo.FUN = mean)
 // R and those packages are absent from the image, so these are
 // restatements of the packages' published algorithms (versions unpinned by the
 // reference's DESCRIPTION:8):
@@ -74,7 +78,10 @@ struct WorkD {
 //   d(k, i∪j) = ((s_k+s_i) d(k,i) + (s_k+s_j) d(k,j) - s_k d(i,j)) / (s_i+s_j+s_k)
 // (f_ward, operands in that order) follow the package, so ties resolve as it
 // resolves them.  The surviving node is the larger index.
-template <bool FULL>
+// COMPLETE: the same chain on unsquared distances with the complete-linkage
+// update d(k, i∪j) = max(d(k,i), d(k,j)) (also reducible, so the chain's
+// reciprocal nearest neighbours are the merges; sizes are carried but unused).
+template <bool FULL, bool COMPLETE = false>
 static void nn_chain_ward(WorkD<FULL>& D, std::vector<Step>& out)
 {
     const int64_t N = D.n;
@@ -156,12 +163,16 @@ static void nn_chain_ward(WorkD<FULL>& D, std::vector<Step>& out)
             if (i == i2) continue;
             const double v = size[i];
             const double b = D.at(i, i2), a = D.at(i, i1);
-            D.set(i, i2, ((v + s) * a - v * mn + (v + t) * b) / (s + t + v));
+            if (COMPLETE)
+                D.set(i, i2, a > b ? a : b);
+            else
+                D.set(i, i2, ((v + s) * a - v * mn + (v + t) * b) / (s + t + v));
         }
     }
 }
 
 static void ward_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order);
+static void tree_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order);
 
 static void ward_d2(const double* dist, int64_t N, int32_t* merge, double* height, int32_t* order, bool full)
 {
@@ -189,6 +200,13 @@ static void ward_d2(const double* dist, int64_t N, int32_t* merge, double* heigh
 static void ward_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order)
 {
     for (auto& s : st) s.h = std::sqrt(s.h);
+    tree_finish(st, N, merge, height, order);
+}
+
+// The same without the sqrt (h: the merge heights as they are returned):
+// scc_hclust_complete's heights are entries of its input.
+static void tree_finish(std::vector<Step>& st, int64_t N, int32_t* merge, double* height, int32_t* order)
+{
     std::stable_sort(st.begin(), st.end(), [](const Step& x, const Step& y) { return x.h < y.h; });
     // union-find: the k-th merge in height order becomes node N + k
     std::vector<int64_t> parent(2 * N - 1, 0);
@@ -500,6 +518,94 @@ SCC_API int scc_hclust_ward_d2(const double* dist, int64_t n, int32_t* merge, do
     const bool full = (double)n * (double)n * 8.0 <= 16e9;
     try {
         ward_d2(dist, n, merge, height, order, full);
+    } catch (const std::bad_alloc&) {
+        return SCC_ERR_OOM;
+    }
+    return SCC_OK;
+}
+
+// stats::hclust(d, "complete") for the heatmap's gene rows (cellTypeDEPlot.R:225-253:
+// ComplexHeatmap's default row clustering).  The NN-chain above with the max
+// update on a full symmetric working copy (n is |U|: a few thousand at most);
+// heights are entries of dist, never recomputed.
+SCC_API int scc_hclust_complete(const double* dist, int64_t n, int32_t* merge, double* height, int32_t* order)
+{
+    if (!dist || !merge || !height || n < 2 || n > (int64_t)INT32_MAX) return SCC_ERR_INVALID;
+    const int64_t M = n * (n - 1) / 2;
+    for (int64_t k = 0; k < M; ++k)
+        if (!std::isfinite(dist[k])) return SCC_ERR_NONFINITE;
+    try {
+        std::vector<Step> st;
+        st.reserve((size_t)n);
+        WorkD<true> D{n, std::vector<double>((size_t)(n * n), 0.0)};
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = j + 1; i < n; ++i) D.set(i, j, dist[pidx(n, i, j)]);
+        nn_chain_ward<true, true>(D, st);
+        tree_finish(st, n, merge, height, order);
+    } catch (const std::bad_alloc&) {
+        return SCC_ERR_OOM;
+    }
+    return SCC_OK;
+}
+
+// stats::reorder.dendrogram(as.dendrogram(tree), wts, agglo.FUN = mean): rows
+// of merge refer to earlier rows only, so one pass in row order gives every
+// node its value before its parent needs it (no recursion: a chain-shaped tree
+// is n deep).  mean() of the two values is R's: a long-double sum, one
+// correction pass.
+SCC_API int scc_dendro_reorder(const int32_t* merge, int64_t n, const double* wts, int32_t* merge_out,
+                               int32_t* order_out)
+{
+    if (!merge || !wts || n < 2 || n > (int64_t)INT32_MAX) return SCC_ERR_INVALID;
+    const int64_t nm = n - 1;
+    try {
+        std::vector<double> val((size_t)nm);
+        std::vector<int64_t> size((size_t)nm);
+        std::vector<int32_t> m((size_t)(2 * nm));
+        std::vector<uint8_t> used((size_t)(n + nm), 0);  // every leaf and every row but the root is a child once
+        for (int64_t k = 0; k < nm; ++k) {
+            int32_t c[2] = {merge[k], merge[k + nm]};
+            double v[2];
+            int64_t s = 0;
+            for (int q = 0; q < 2; ++q) {
+                if (c[q] == 0 || c[q] < -n || c[q] > k) return SCC_ERR_INVALID;
+                const size_t slot = c[q] < 0 ? (size_t)(-c[q] - 1) : (size_t)(n + c[q] - 1);
+                if (used[slot]) return SCC_ERR_INVALID;
+                used[slot] = 1;
+                v[q] = c[q] < 0 ? wts[-c[q] - 1] : val[(size_t)(c[q] - 1)];
+                s += c[q] < 0 ? 1 : size[(size_t)(c[q] - 1)];
+            }
+            if (v[1] < v[0]) {  // increasing value; an equal (or unordered) pair keeps its order
+                std::swap(c[0], c[1]);
+                std::swap(v[0], v[1]);
+            }
+            long double mu = ((long double)v[0] + (long double)v[1]) / 2.0L;
+            mu += (((long double)v[0] - mu) + ((long double)v[1] - mu)) / 2.0L;
+            val[(size_t)k] = (double)mu;
+            size[(size_t)k] = s;
+            m[(size_t)k] = c[0];
+            m[(size_t)(k + nm)] = c[1];
+        }
+        if (size[(size_t)(nm - 1)] != n) return SCC_ERR_INVALID;
+        if (order_out) {
+            std::vector<std::pair<int64_t, int64_t>> q;  // (first position, row)
+            q.push_back({0, nm - 1});
+            while (!q.empty()) {
+                const auto cur = q.back();
+                q.pop_back();
+                int64_t pos = cur.first;
+                const int32_t c1 = m[(size_t)cur.second], c2 = m[(size_t)(cur.second + nm)];
+                if (c1 < 0) {
+                    order_out[pos++] = -c1;
+                } else {
+                    q.push_back({pos, c1 - 1});
+                    pos += size[(size_t)(c1 - 1)];
+                }
+                if (c2 < 0) order_out[pos] = -c2;
+                else q.push_back({pos, c2 - 1});
+            }
+        }
+        if (merge_out) std::memcpy(merge_out, m.data(), sizeof(int32_t) * m.size());
     } catch (const std::bad_alloc&) {
         return SCC_ERR_OOM;
     }

@@ -330,3 +330,20 @@ hipError_t scc_launch_wv_advance(double* C, int N, scc_wv_state* S, int* chain, 
                                  hipStream_t st);
 hipError_t scc_launch_wv_gather_core(const double* P, int N, const int* core, int cs, double* block, hipStream_t st);
 }
+
+// ---- heatmap inputs (scc_heatmap.hip) -----------------------------------------
+// All read the gathered panel Xc [Npad][ld] of scc_launch_gather.
+extern "C" {
+int scc_gene_dist_slabs(int Npad, int ld);             // cell slabs of one call
+size_t scc_gene_dist_slab_doubles(int Npad, int ld);   // their scratch
+// out: device, packed R `dist` order, nu (nu - 1) / 2 doubles
+hipError_t scc_launch_gene_dist(const double* Xc, int Npad, int nu, int ld, double* slabs, double* out,
+                                hipStream_t st);
+size_t scc_hm_range_scratch_bytes(void);
+// out: {min x, max x, min |x|, max |x|} over rows [0, N), columns [0, nu); nbad: non-finite values
+hipError_t scc_launch_hm_range(const double* Xc, int N, int nu, int ld, void* scratch, double* out,
+                               unsigned int* nbad, hipStream_t st);
+// R [width][nu]: bin means over cell[floor(b N / width) .. floor((b + 1) N / width)) (0-based ids)
+hipError_t scc_launch_heatmap_raster(const double* Xc, int N, int nu, int ld, const int* cell, int width, double* R,
+                                     hipStream_t st);
+}
