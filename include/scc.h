@@ -271,6 +271,51 @@ SCC_API int scc_de_result_log_threshold(const scc_de_result* r, double* log_thr)
 SCC_API int scc_de_result_nodg(const scc_de_result* r, int32_t* nodg /* [N] */);
 SCC_API void scc_de_result_destroy(scc_de_result* r);
 
+/* ---- one-vs-rest marker genes: every cluster against the rest, one pass ----
+ * The reference README's FindAllMarkers step (README.md:143-153) on the
+ * engine.  Kept clusters are the codes 0..K-1; cells with code -1 take part
+ * in nothing.  For each cluster a, cells.1 = {code == a}, cells.2 = {code >= 0
+ * and code != a}, and the result for a is what ComputePairWiseDE(cells.1,
+ * cells.2, test.use = "wilcox") returns (Fast:73-355) followed by the caller's
+ * rules (Fast:376-392):
+ *   pct1 = 100 cnt_a / n_a, pct2 = 100 (cnt_sel - cnt_a) / n_rest (exact);
+ *   avg_logFC = log(mean_a(expm1 x) + 1) - log(mean_rest(expm1 x) + 1), the
+ *     rest's mean from the double-double sums of the other clusters added in
+ *     cluster order and divided once by n_rest;
+ *   filters max(pct1, pct2) > min_per_cent, expm1(m1) > 0 || expm1(m2) > 0,
+ *     |avg_logFC| > log_fc_thrs (only_pos: avg_logFC > log_fc_thrs), strict;
+ *   wilcox.test's rule: exact iff n_a < 50, n_rest < 50 and no ties, else the
+ *     continuity-corrected normal p;
+ *   rows in order(p, -avg_logFC), BH with n = the cluster's tested rows, a
+ *     cluster with <= 1 tested row contributes nothing, flags as in
+ *     scc_de_result_rows, the union unique() over a = 0..K-1 in row order.
+ * One sort of a gene's nonzeros serves all K tests: the statistics are exact
+ * integers (2U_a equals the sum over b != a of the all-pairs 2U_ab).
+ * The result is an ordinary scc_de_result with the K clusters in the place of
+ * pairs: scc_de_result_counts reports n_pairs = K; scc_de_result_rows gives
+ * cluster-major rows (pct1: cluster a, pct2: the rest, u2 = 2W of cluster a,
+ * ties = the selection's tie term, the same for every cluster of a gene);
+ * scc_de_result_union and scc_de_result_nodg as for scc_de_run;
+ * scc_de_result_pair_vectors (p, logfc, u2; q and de NULL) and
+ * scc_de_result_ties give the dense [K][G] arrays -- with test_all = 1 also
+ * for the (cluster, gene) cells the filters drop, else p = NaN, u2 = ties = -1
+ * there.
+ * Limits: test = SCC_TEST_WILCOX only (SCC_TEST_T and SCC_TEST_BIMOD return
+ * SCC_ERR_UNSUPPORTED); K <= 128 (more: SCC_ERR_UNSUPPORTED); every cluster
+ * needs >= 3 cells (min.cells.group; else SCC_ERR_RSTOP, as scc_de_run);
+ * there is no SLOW form; no subsampling, no min.diff.pct; the call runs on the
+ * context's first device only. */
+typedef struct {
+    int32_t top_n, only_pos, test /* SCC_TEST_WILCOX only */, test_all;
+    double q_val_thrs, log_fc_thrs, min_per_cent;
+    int32_t reserved[4]; /* must be zero (else SCC_ERR_INVALID) */
+} scc_markers_params;
+SCC_API int scc_de_markers(scc_ctx* ctx, const scc_dataset* ds, const int32_t* code /* host [N] */, int32_t K,
+                           const scc_markers_params* params, scc_de_result** out);
+/* The dense tie terms [n_pairs][G] of an scc_de_markers result (every row of a
+ * tested gene holds the same value). */
+SCC_API int scc_de_result_ties(const scc_de_result* r, int64_t* ties);
+
 /* ---- stage 3: cell x cell distance on the DE-gene union ---------------- */
 /* Packed lower triangle in R `dist` order (column-major: (1,0),(2,0),...,
  * (N-1,0),(2,1),...), length N(N-1)/2.  out_kind SCC_PTR_HOST copies to the

@@ -307,3 +307,36 @@ reclusterDEConsensus <- function(dataMatrix, consensusClusterLabels, method = "W
             plotName)
   out
 }
+
+# One-vs-rest marker genes of every selected cluster in one engine pass
+# (scc_de_markers): the reference README's annotation step,
+#   FindAllMarkers(min.pct = minPerCent / 100, logfc.threshold = logFCThrs, only.pos = onlyPos)
+#   %>% group_by(cluster) %>% top_n(NumbertopDEGenes, avg_logFC)         (README.md:143-153)
+# with ComputePairWiseDE's rules for each cluster against all other selected
+# cells (Fast:73-355, 376-392; test.use = "wilcox" only).  Clusters are selected
+# as in reclusterDEConsensusFast (.scc_codes).  Returns a Seurat-shaped data
+# frame (p_val, avg_logFC, pct.1, pct.2, p_val_adj, cluster, gene), every tested
+# row, cluster-major and inside a cluster in order(p_val, -avg_logFC); the
+# columns kept (p_val_adj < qValThrs in a cluster with more than one row) and top
+# (kept and within the top NumbertopDEGenes of |avg_logFC|, ties kept) mark what
+# the reference's filter and top_n leave; attr(, "deGeneUnion") is unique() over
+# the top rows.
+sccFindAllMarkers <- function(dataMatrix, clusterLabels, minClusterSize = 10, minPerCent = 20,
+                              logFCThrs = 0.5, qValThrs = 0.1, onlyPos = FALSE,
+                              NumbertopDEGenes = 30) {
+  sel <- .scc_codes(clusterLabels, dataMatrix, minClusterSize)
+  if (length(sel$clusters) < 2) stop("need at least two clusters with > minClusterSize cells")
+  h <- .scc_dataset(dataMatrix)
+  on.exit(.Call("C_scc_release", h), add = TRUE)
+  res <- .Call("C_scc_markers", h, sel$code, length(sel$clusters), as.double(qValThrs),
+               as.double(logFCThrs), as.double(minPerCent), as.integer(NumbertopDEGenes),
+               isTRUE(onlyPos))
+  genes <- rownames(dataMatrix)
+  out <- data.frame(p_val = res$p_val, avg_logFC = res$avg_logFC, pct.1 = res$pct.1, pct.2 = res$pct.2,
+                    p_val_adj = res$p_val_adj,
+                    cluster = factor(sel$clusters[res$cluster], levels = sel$clusters),
+                    gene = genes[res$gene], kept = res$kept, top = res$top,
+                    check.names = FALSE, stringsAsFactors = FALSE)
+  attr(out, "deGeneUnion") <- genes[res$union]
+  out
+}

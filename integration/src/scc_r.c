@@ -11,6 +11,9 @@
  *                   pointer that the DE and distance calls share
  *   C_scc_de_fast   R/reclusterDEConsensusFast.R:57-392 (pair loop, ComputePairWiseDE, top_n, unique)
  *   C_scc_de_slow   R/reclusterDEConsensus.R:32-227
+ *   C_scc_markers   the reference README's FindAllMarkers step (README.md:143-153):
+ *                   ComputePairWiseDE(cluster, all other selected cells) for every
+ *                   cluster, one engine pass (scc_de_markers)
  *   C_scc_distance  R/reclusterDEConsensusFast.R:398-400 (prcomp_irlba + dist), :403 (1 - cor)
  *   C_scc_release   frees the device copy early (the finalizer does it otherwise)
  *   C_scc_devices   nCores (Fast:33,61-65) -> the context's device list
@@ -183,6 +186,70 @@ SEXP C_scc_de_fast(SEXP h, SEXP code, SEXP K, SEXP qthr, SEXP lfc, SEXP minpct, 
     SET_VECTOR_ELT(out, 0, uni);
     SET_VECTOR_ELT(out, 1, nodg);
     UNPROTECT(3);
+    return out;
+}
+
+/* One-vs-rest markers of every cluster (scc_de_markers).  Returns list(cluster =
+ * int (1-based cluster index per row), gene = int (1-based gene row), p_val,
+ * avg_logFC, pct.1, pct.2, p_val_adj = double, kept, top = logical, union = int
+ * (1-based gene rows)); rows cluster-major, in order(p_val, -avg_logFC) inside a
+ * cluster.  pct.1 / pct.2 are fractions as Seurat reports them (the engine's
+ * per cent / 100). */
+SEXP C_scc_markers(SEXP h, SEXP code, SEXP K, SEXP qthr, SEXP lfc, SEXP minpct, SEXP topn, SEXP onlypos)
+{
+    ensure_ctx();
+    int N = 0;
+    scc_dataset* ds = ds_of(h, NULL, &N);
+    if (XLENGTH(code) != N) Rf_error("scConsensus engine: %d cluster codes for %d cells", (int)XLENGTH(code), N);
+    scc_markers_params prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.q_val_thrs = Rf_asReal(qthr);
+    prm.log_fc_thrs = Rf_asReal(lfc);
+    prm.min_per_cent = Rf_asReal(minpct);
+    prm.top_n = Rf_asInteger(topn);
+    prm.only_pos = Rf_asLogical(onlypos) == TRUE;
+    prm.test = SCC_TEST_WILCOX;
+    scc_de_result* r = NULL;
+    int rc = scc_de_markers(g_ctx, ds, INTEGER(code), Rf_asInteger(K), &prm, &r);
+    if (rc != SCC_OK) { /* includes SCC_ERR_RSTOP: a cluster of fewer than 3 cells stops in R too */
+        if (r) scc_de_result_destroy(r);
+        check(rc);
+    }
+    int32_t nclu = 0, nu = 0;
+    int64_t nrows = 0;
+    scc_de_result_counts(r, &nclu, &nrows, &nu);
+    const char* names[] = {"cluster", "gene", "p_val", "avg_logFC", "pct.1", "pct.2", "p_val_adj", "kept", "top",
+                           "union", ""};
+    SEXP out = PROTECT(Rf_mkNamed(VECSXP, names));
+    SEXP cl = PROTECT(Rf_allocVector(INTSXP, nrows)), gene = PROTECT(Rf_allocVector(INTSXP, nrows));
+    SEXP p = PROTECT(Rf_allocVector(REALSXP, nrows)), fc = PROTECT(Rf_allocVector(REALSXP, nrows));
+    SEXP p1 = PROTECT(Rf_allocVector(REALSXP, nrows)), p2 = PROTECT(Rf_allocVector(REALSXP, nrows));
+    SEXP q = PROTECT(Rf_allocVector(REALSXP, nrows));
+    SEXP kept = PROTECT(Rf_allocVector(LGLSXP, nrows)), top = PROTECT(Rf_allocVector(LGLSXP, nrows));
+    SEXP uni = PROTECT(Rf_allocVector(INTSXP, nu));
+    int32_t* per = (int32_t*)R_alloc(nclu > 0 ? nclu : 1, sizeof(int32_t));
+    uint8_t* fl = (uint8_t*)R_alloc(nrows > 0 ? nrows : 1, 1);
+    rc = scc_de_result_rows(r, per, INTEGER(gene), REAL(p), REAL(q), REAL(fc), REAL(p1), REAL(p2), NULL, NULL, fl);
+    scc_de_result_union(r, INTEGER(uni));
+    scc_de_result_destroy(r);
+    if (rc != SCC_OK) {
+        UNPROTECT(11);
+        check(rc);
+    }
+    int64_t k = 0;
+    for (int a = 0; a < nclu; ++a)
+        for (int i = 0; i < per[a]; ++i, ++k) INTEGER(cl)[k] = a + 1;
+    for (k = 0; k < nrows; ++k) {
+        INTEGER(gene)[k] += 1;
+        REAL(p1)[k] /= 100.0;
+        REAL(p2)[k] /= 100.0;
+        LOGICAL(kept)[k] = (fl[k] & 1) != 0;
+        LOGICAL(top)[k] = (fl[k] & 2) != 0;
+    }
+    for (int u = 0; u < nu; ++u) INTEGER(uni)[u] += 1;
+    SEXP cols[] = {cl, gene, p, fc, p1, p2, q, kept, top, uni};
+    for (int f = 0; f < 10; ++f) SET_VECTOR_ELT(out, f, cols[f]);
+    UNPROTECT(11);
     return out;
 }
 
@@ -513,6 +580,7 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_release", (DL_FUNC)&C_scc_release, 1},
     {"C_scc_de_fast", (DL_FUNC)&C_scc_de_fast, 8},
     {"C_scc_de_slow", (DL_FUNC)&C_scc_de_slow, 6},
+    {"C_scc_markers", (DL_FUNC)&C_scc_markers, 8},
     {"C_scc_distance", (DL_FUNC)&C_scc_distance, 4},
     {"C_scc_si", (DL_FUNC)&C_scc_si, 1},
     {"C_scc_devices", (DL_FUNC)&C_scc_devices, 1},

@@ -46,6 +46,7 @@ EXPORTS = [
     "scc_de_run", "scc_de_shard_bytes", "scc_de_run_shard", "scc_de_finish", "scc_de_run_shard_records",
     "scc_de_finish_records", "scc_de_finish_records_pairs", "scc_de_union_first_occ", "scc_de_result_counts", "scc_de_result_union", "scc_de_result_rows",
     "scc_de_result_pair_vectors", "scc_de_result_log_threshold", "scc_de_result_nodg", "scc_de_result_destroy",
+    "scc_de_markers", "scc_de_result_ties",
     "scc_distance", "scc_de_distance", "scc_distance_cols", "scc_pca_shard_colsum", "scc_pca_shard_gram", "scc_pca_shard_scores", "scc_pca_shard_eigen", "scc_pca_shard_project",
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
@@ -73,6 +74,12 @@ class DeParams(ctypes.Structure):
                 ("log_fc_thrs", ctypes.c_double), ("min_per_cent", ctypes.c_double), ("fc_thrs", ctypes.c_double),
                 ("mean_scaling_factor", ctypes.c_double), ("test_all", ctypes.c_int32),
                 ("test", ctypes.c_int32)]
+
+
+class MarkersParams(ctypes.Structure):
+    _fields_ = [("top_n", ctypes.c_int32), ("only_pos", ctypes.c_int32), ("test", ctypes.c_int32),
+                ("test_all", ctypes.c_int32), ("q_val_thrs", ctypes.c_double), ("log_fc_thrs", ctypes.c_double),
+                ("min_per_cent", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
 
 
 _lib = None
@@ -132,6 +139,8 @@ def load():
         "scc_de_result_log_threshold": (ctypes.c_int, [vp, P(dbl)]),
         "scc_de_result_nodg": (ctypes.c_int, [vp, vp]),
         "scc_de_result_destroy": (None, [vp]),
+        "scc_de_markers": (ctypes.c_int, [vp, vp, vp, i32, P(MarkersParams), P(vp)]),
+        "scc_de_result_ties": (ctypes.c_int, [vp, vp]),
         "scc_distance": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, vp, i32, i32]),
         "scc_de_distance": (ctypes.c_int, [vp, vp, vp, i32, P(DeParams), i32, i32, vp, i32, i32, P(vp)]),
         "scc_distance_cols": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, i64, i64, vp, i32, i32]),
@@ -205,6 +214,7 @@ class DeResult:
     logfc: np.ndarray | None = None    # [P, G]
     u2: np.ndarray | None = None       # [P, G]
     de: np.ndarray | None = None       # SLOW [P, G]
+    ties: np.ndarray | None = None     # [K, G] (de_markers, fetch="all")
     log_thr: float = 0.0
     status: int = 0
     message: str = ""
@@ -336,6 +346,25 @@ class Engine:
         rc = self.lib.scc_de_run(self.ctx, ds.handle, _ptr(code), K, ctypes.byref(prm), ctypes.byref(r))
         return self._collect(r, rc, ds, mode, K, fetch)
 
+    def de_markers(self, ds: Dataset, code, K, q_val_thrs=0.1, log_fc_thrs=0.5, min_per_cent=20.0, top_n=30,
+                   only_pos=False, fetch="rows", test_all=None, test="wilcox") -> DeResult:
+        """One-vs-rest marker genes (scc_de_markers): cluster a against every
+        other kept cell, for all K clusters in one engine pass.  The result has
+        the K clusters in the place of pairs: ``rows`` is cluster-major
+        (``pair_tested[a]`` rows of cluster a; pct1 the cluster, pct2 the rest).
+        fetch="all" adds the dense [K, G] ``p``, ``logfc``, ``u2`` and ``ties``;
+        test_all (default: with fetch="all") computes them for the cells the
+        feature filters drop too."""
+        if test not in _TEST_CODES:
+            raise ValueError(f"test must be 'wilcox', 't' or 'bimod', not {test!r}")
+        code = np.ascontiguousarray(code, np.int32)
+        prm = MarkersParams(top_n, 1 if only_pos else 0, _TEST_CODES[test],
+                            1 if (fetch == "all" if test_all is None else test_all) else 0, q_val_thrs, log_fc_thrs,
+                            min_per_cent)
+        r = ctypes.c_void_p()
+        rc = self.lib.scc_de_markers(self.ctx, ds.handle, _ptr(code), K, ctypes.byref(prm), ctypes.byref(r))
+        return self._collect(r, rc, ds, SCC_DE_FAST, K, fetch, ties=True)
+
     @staticmethod
     def _de_params(mode, q_val_thrs, log_fc_thrs, min_per_cent, top_n, fc_thrs, mean_scaling_factor, test_all,
                    test="wilcox"):
@@ -423,7 +452,7 @@ class Engine:
                                                     ctypes.byref(nu)))
         return out[: nu.value].copy()
 
-    def _collect(self, r, rc, ds, mode, K, fetch) -> DeResult:
+    def _collect(self, r, rc, ds, mode, K, fetch, ties=False) -> DeResult:
         msg = ""
         if rc != SCC_OK:
             msg = self.lib.scc_ctx_last_error(self.ctx).decode()
@@ -459,6 +488,9 @@ class Engine:
                     pv, lf, u2 = np.zeros((P, G)), np.zeros((P, G)), np.zeros((P, G), np.int64)
                     self._check(self.lib.scc_de_result_pair_vectors(r, _ptr(pv), None, _ptr(lf), _ptr(u2), None))
                     out.p, out.logfc, out.u2 = pv, lf, u2
+                    if ties:
+                        out.ties = np.zeros((P, G), np.int64)
+                        self._check(self.lib.scc_de_result_ties(r, _ptr(out.ties)))
             else:
                 pv, qv, lf = np.zeros((P, G)), np.zeros((P, G)), np.zeros((P, G))
                 u2, de = np.zeros((P, G), np.int64), np.zeros((P, G), np.uint8)

@@ -388,3 +388,47 @@ def reclusterDEConsensus(dataMatrix, consensusClusterLabels, method="Wilcoxon", 
         ret["_details"] = {"clusters": names, "code": code, "de": res, "dist": d, "union_idx": uni}
     ds.close()
     return ret
+
+
+def findAllMarkers(dataMatrix, clusterLabels, minClusterSize=10, minPerCent=20, logFCThrs=0.5, qValThrs=0.1,
+                   onlyPos=False, NumbertopDEGenes=30, device=0, *, gene_names=None, cluster_order=None):
+    """One-vs-rest marker genes of every cluster in one engine pass
+    (scc_de_markers): the reference README's ``FindAllMarkers(min.pct,
+    logfc.threshold, only.pos)`` followed by ``top_n(NumbertopDEGenes,
+    avg_logFC)`` per cluster (README.md:143-153), each cluster tested against
+    all other selected cells with ComputePairWiseDE's rules (Fast:73-355).
+    Clusters are selected as in the two recluster functions
+    (``select_clusters``: more than minClusterSize cells, no "grey").
+
+    Returns ``{"markers": {cluster name: table}, "union": [gene names],
+    "union_idx": int32 rows, "clusters": names}``; a table is a dict of
+    equal-length arrays ``gene``, ``gene_idx``, ``p_val``, ``avg_logFC``,
+    ``pct.1``, ``pct.2``, ``p_val_adj``, ``kept`` (p_val_adj < qValThrs in a
+    cluster with more than one tested row) and ``top`` (kept and within the top
+    NumbertopDEGenes of |avg_logFC|, ties kept), rows in R's order(p_val,
+    -avg_logFC).  ``union`` is unique() over the clusters' top rows in order."""
+    eng = _engine(device)
+    m = _as_matrix(dataMatrix)
+    G = m[-2] if m[0] in ("csc", "csr") else m[1].shape[0]
+    names, code = select_clusters(clusterLabels, minClusterSize, cluster_order)
+    if len(names) < 2:
+        raise ValueError("need at least two clusters with > minClusterSize cells")
+    ds = _upload(eng, m)
+    try:
+        res = eng.de_markers(ds, code, len(names), q_val_thrs=qValThrs, log_fc_thrs=logFCThrs,
+                             min_per_cent=float(minPerCent), top_n=NumbertopDEGenes, only_pos=bool(onlyPos),
+                             fetch="rows")
+    finally:
+        ds.close()
+    if res.status == nat.SCC_ERR_RSTOP:
+        raise RuntimeError(res.message)
+    gnames = np.asarray(gene_names if gene_names is not None else [f"gene{g}" for g in range(G)], dtype=object)
+    r = res.rows
+    starts = np.concatenate([[0], np.cumsum(r.pair_tested)]).astype(np.int64)
+    markers = {}
+    for a, name in enumerate(names):
+        s = slice(int(starts[a]), int(starts[a + 1]))
+        markers[name] = {"gene": gnames[r.gene[s]], "gene_idx": r.gene[s].copy(), "p_val": r.p[s].copy(),
+                         "avg_logFC": r.avg_logfc[s].copy(), "pct.1": r.pct1[s].copy(), "pct.2": r.pct2[s].copy(),
+                         "p_val_adj": r.q[s].copy(), "kept": r.de[s].copy(), "top": r.top[s].copy()}
+    return {"markers": markers, "union": list(gnames[res.union]), "union_idx": res.union, "clusters": names}

@@ -1,6 +1,8 @@
 // scc_de.cpp — the DE driver behind scc_de_run and the gene-shard / record
 // entry points (include/scc.h): one engine run as a list of phases (de_run),
-// the device-list run, the group-pair runs for K > 128, the result accessors.
+// the device-list run, the group-pair runs for K > 128, the one-vs-rest marker
+// run (scc_de_markers: its own phase list over the same phases), the result
+// accessors.
 //
 // The whole DE stage is one stream-ordered launch sequence (the bigger genes
 // run on a side stream concurrently with the LDS-resident ones); the host
@@ -74,6 +76,7 @@ struct DePlan {
     int64_t GK, nnz1;
     size_t PG;
     bool fast, norank, all_pairs;
+    bool markers;  // the one-vs-rest run (scc_de_markers): P = K "pairs", its own rank kernel, no all-pairs rank lists
     int test;
     std::vector<int> nclu;
     // the host cell tables (c->host_tables; not in a finish stage): sizes and offsets
@@ -102,6 +105,7 @@ struct DeBuffers {
     ScRankItem *d_items, *d_sbk;
     unsigned int* d_hbg;
     dd *d_wexp, *d_gexp;
+    dd* d_sume;  // [K][G] undivided expm1 sums (the one-vs-rest run only; else nullptr)
     double *d_mx, *d_me, *d_vx, *d_mpos, *d_m2pos, *d_minpos, *d_maxpos;
     double *d_p, *d_lfc, *d_pct1, *d_pct2;
     long long *d_u2, *d_t;
@@ -333,10 +337,13 @@ static int de_alloc(scc_ctx* c, const DePlan& pl, DeBuffers* b)
         WS("gstart", G + 1, b->d_gstart);
         WS("scan", scc_scan_scratch_blocks(G) + 1, b->d_scan);
         WS("keys", nnz1, b->d_keys);
-        WS("gix", 2 * (size_t)nnz1, b->d_gix);
-        WS("gcode", nnz1, b->d_gcode);
-        WS("gwin", nnz1, b->d_gwin);
-        WS("gsc", nnz1, b->d_gsc);
+        const bool lists = !pl.markers;  // the all-pairs rank stage's work lists
+        if (lists) {
+            WS("gix", 2 * (size_t)nnz1, b->d_gix);
+            WS("gcode", nnz1, b->d_gcode);
+            WS("gwin", nnz1, b->d_gwin);
+            WS("gsc", nnz1, b->d_gsc);
+        }
         WS("keys2", nnz1, b->d_keys2);
         WS("codes2", nnz1, b->d_codes2);
         {
@@ -344,10 +351,14 @@ static int de_alloc(scc_ctx* c, const DePlan& pl, DeBuffers* b)
             if ((rc = ws_get(c, "wexp", sizeof(double) * 2 * (nwaves + 1), &p))) return rc;
             b->d_wexp = (dd*)p;
             b->d_gexp = (dd*)((char*)p + sizeof(double) * 2 * nwaves);
+            if (pl.markers) {  // the clusters' undivided expm1 sums: the rest's mean divides a sum of them
+                if ((rc = ws_get(c, "sum_e", sizeof(double) * 2 * (size_t)GK, &p))) return rc;
+                b->d_sume = (dd*)p;
+            }
         }
         // (the mirror's build and the transpose scan the count rows' columns; a regroup of a built mirror does not)
         if (!(pl.try_mirror && pl.ds->m_gptr)) WS("colscan", scc_ingest_colscan_scratch(nc, G), b->d_cscr);
-        WS("splitg", (size_t)G, b->d_splitg);
+        if (lists) WS("splitg", (size_t)G, b->d_splitg);
         WS("counts", SCC_NCOUNTS * SCC_CNT_STRIDE, b->d_counts);
         WS("mx", GK, b->d_mx);
         WS("me", GK, b->d_me);
@@ -359,12 +370,14 @@ static int de_alloc(scc_ctx* c, const DePlan& pl, DeBuffers* b)
         WS("minpos", bimod ? GK : 1, b->d_minpos);
         WS("maxpos", bimod ? GK : 1, b->d_maxpos);
         WS("acc", pl.acc_n, b->d_acc);
-        WS("items", 3 * (size_t)item_cap, b->d_items);
-        WS("sbuckets", (size_t)bucket_cap, b->d_sbk);
-        WS("hbg", (size_t)bucket_cap * K, b->d_hbg);
-        WS("genebk", 2 * (size_t)G, b->d_genebk);
-        WS("gkmin", (size_t)G, b->d_gkmin);
-        if (!pl.norank) {
+        if (lists) {
+            WS("items", 3 * (size_t)item_cap, b->d_items);
+            WS("sbuckets", (size_t)bucket_cap, b->d_sbk);
+            WS("hbg", (size_t)bucket_cap * K, b->d_hbg);
+            WS("genebk", 2 * (size_t)G, b->d_genebk);
+            WS("gkmin", (size_t)G, b->d_gkmin);
+        }
+        if (lists && !pl.norank) {
             WS("gene_tp", (size_t)G * P, b->gene_tp);
             WS("gene_nt", (size_t)G, b->gene_nt);
             if (scc_rank_tables_global(pl.ntp_max, K)) {  // items' tested-pair tables in HBM, one slice per workgroup
@@ -609,6 +622,7 @@ static int gene_stats(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
     S.mean_x = B.d_mx, S.mean_e = B.d_me, S.cnt_pos = B.d_cntpos, S.cnt_neg = B.d_cntneg;
     S.var_x = B.d_vx;
     S.mean_pos = B.d_mpos, S.m2_pos = B.d_m2pos, S.min_pos = B.d_minpos, S.max_pos = B.d_maxpos;
+    S.sum_e = B.d_sume;
     HIPCHK(c, scc_launch_gene_stats(&S, c->s0));
     return SCC_OK;
 }
@@ -1092,6 +1106,117 @@ static int de_run(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_
     if (n_union < 0 || n_union > pl.G) return fail(c, SCC_ERR_HIP, "union size out of range");
     *out = build_result(c, pl, B, n_union);
     // selection-stage conditions (k_pair_select), reported after the result is built
+    return de_error(c, err_bits, AT_RESULT);
+}
+
+// ---------------------------------------------------------------- one-vs-rest markers
+// scc_de_markers: for every cluster a, ComputePairWiseDE(cells.1 = a, cells.2 =
+// the other kept cells) and the caller's selection (Fast:229-351, 376-392), in
+// one engine pass.  The run is a DE_FULL FAST plan whose "pairs" are the K
+// clusters: every [P][G] field is [K][G], so the ingest, the statistics, the
+// selection (BH, top-N, first-occurrence union, tested-rows > 1) and the
+// result are the all-pairs route's own phases; the filter, the rank kernel
+// (one sort per gene serves all K tests, scc_rank_rest.hip) and the test are
+// the one-vs-rest ones.  It runs on the context's first device.
+static int markers_plan(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_t K,
+                        const scc_de_params* dp, DePlan* p)
+{
+    int rc = de_plan(c, ds, code, K, dp, DE_FULL, 0, ds->G, nullptr, nullptr, p);
+    if (rc) return rc;
+    p->markers = true;
+    p->P = K;
+    p->PG = (size_t)p->GK;
+    p->acc_n = (size_t)p->GK + (size_t)p->G;  // R2 per (cluster, gene), T per gene
+    return SCC_OK;
+}
+
+// the largest group of an exact test: cluster a and its rest both below 50 cells
+static int markers_exact_size(const std::vector<int>& nclu)
+{
+    int nsel = 0, m = 0;
+    for (int v : nclu) nsel += v;
+    for (int v : nclu)
+        if (v < 50 && nsel - v < 50) m = std::max(m, std::max(v, nsel - v));
+    return m;
+}
+
+static ScRestTestLaunch rest_launch(const scc_ctx* c, const DePlan& pl, const DeBuffers& B, int only_pos)
+{
+    ScRestTestLaunch T{};
+    T.K = pl.K, T.G = pl.G, T.only_pos = only_pos, T.all = pl.all_pairs ? 1 : 0;
+    T.min_pct = pl.prm->min_per_cent, T.lfc_thr = pl.prm->log_fc_thrs;
+    T.n_clu = B.d_nclu, T.sum_e = B.d_sume, T.cnt_pos = B.d_cntpos, T.cnt_neg = B.d_cntneg;
+    T.accR = B.d_acc, T.accT = B.d_acc + pl.PG;
+    T.wtab = c->d_wtab, T.woff = c->d_woff;
+    T.out_p = B.d_p, T.out_lfc = B.d_lfc, T.out_pct1 = B.d_pct1, T.out_pct2 = B.d_pct2;
+    T.out_u2 = B.d_u2, T.out_t = B.d_t, T.out_flags = B.d_flags;
+    return T;
+}
+
+static int rank_rest_stage(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
+{
+    Scope sc(c, "rank_rest", c->s0);
+    ScRestRankLaunch L{};
+    L.gstart = gene_starts(pl, B);
+    L.keys = B.d_keys;
+    L.G = pl.G, L.K = pl.K, L.all = pl.all_pairs ? 1 : 0;
+    L.coff = B.d_cnt, L.cl_cc = B.d_clcc, L.flags = B.d_flags;
+    L.keys2 = B.d_keys2, L.codes2 = B.d_codes2;
+    L.accR = B.d_acc, L.accT = B.d_acc + pl.PG;
+    HIPCHK(c, scc_launch_rank_rest(&L, c->s0));
+    return SCC_OK;
+}
+
+extern "C" int scc_de_markers(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_t K,
+                              const scc_markers_params* mp, scc_de_result** out)
+{
+    if (!c || !ds || !code || !mp || !out) return fail(c, SCC_ERR_INVALID, "scc_de_markers: null argument");
+    *out = nullptr;
+    if (ds->ctx != c) return fail(c, SCC_ERR_INVALID, "dataset belongs to another context");
+    if (mp->test == SCC_TEST_T || mp->test == SCC_TEST_BIMOD)
+        return fail(c, SCC_ERR_UNSUPPORTED, "scc_de_markers: SCC_TEST_WILCOX only");
+    if (mp->test != SCC_TEST_WILCOX) return fail(c, SCC_ERR_INVALID, "scc_de_markers: bad test");
+    if (K < 2) return fail(c, SCC_ERR_INVALID, "need at least two clusters");
+    if (K > kMaxK) return fail(c, SCC_ERR_UNSUPPORTED, "scc_de_markers: K > 128 clusters");
+    for (int32_t v : mp->reserved)
+        if (v != 0) return fail(c, SCC_ERR_INVALID, "scc_de_markers: reserved fields must be zero");
+    scc_de_params dp{};
+    dp.mode = SCC_DE_FAST, dp.top_n = mp->top_n, dp.q_val_thrs = mp->q_val_thrs, dp.log_fc_thrs = mp->log_fc_thrs;
+    dp.min_per_cent = mp->min_per_cent, dp.fc_thrs = 1.5, dp.mean_scaling_factor = 5.0;
+    dp.test_all = mp->test_all ? 1 : 0, dp.test = SCC_TEST_WILCOX;
+    int rc;
+    scc_enter(c);
+    DePlan pl{};
+    if ((rc = markers_plan(c, ds, code, K, &dp, &pl))) return rc;
+    DeBuffers B{};
+    if ((rc = de_alloc(c, pl, &B))) return rc;
+    if ((rc = ensure_wtab(c, markers_exact_size(pl.nclu)))) return rc;
+    hipStream_t s0 = c->s0;
+    c->generation++;
+    if ((rc = upload_tables(c, B))) return rc;
+    if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
+    g_ingest_last_path = pl.route;
+    if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
+    if ((rc = gene_stats(c, pl, B))) return rc;
+    const ScRestTestLaunch T = rest_launch(c, pl, B, mp->only_pos ? 1 : 0);
+    {
+        Scope sc(c, "rest_filter", s0);
+        HIPCHK(c, scc_launch_rest_filter(&T, s0));
+    }
+    if ((rc = rank_rest_stage(c, pl, B))) return rc;
+    {
+        Scope sc(c, "rest_test", s0);
+        HIPCHK(c, scc_launch_rest_test(&T, s0));
+    }
+    if ((rc = pair_select(c, pl, B))) return rc;
+    if ((rc = stage_pack(c, pl, B))) return rc;
+    const int n_union = c->h_stage[0], err_bits = c->h_stage[1];
+    if ((rc = de_error(c, err_bits, AT_FULL))) return rc;
+    if ((rc = note_validated(c, pl, B, err_bits))) return rc;
+    if (n_union < 0 || n_union > pl.G) return fail(c, SCC_ERR_HIP, "union size out of range");
+    scc_de_result* r = build_result(c, pl, B, n_union);
+    r->d_t = B.d_t;
+    *out = r;
     return de_error(c, err_bits, AT_RESULT);
 }
 
@@ -1649,6 +1774,14 @@ extern "C" int scc_de_result_nodg(const scc_de_result* r, int32_t* nodg)
     int rc = check_live(r);
     if (rc) return rc;
     return d2h(r->ctx, nodg, r->d_nodg, (size_t)r->N);
+}
+
+extern "C" int scc_de_result_ties(const scc_de_result* r, int64_t* ties)
+{
+    int rc = check_live(r);
+    if (rc) return rc;
+    if (!r->d_t) return fail(r->ctx, SCC_ERR_INVALID, "scc_de_result_ties: an scc_de_markers result only");
+    return d2h(r->ctx, (long long*)ties, r->d_t, (size_t)r->P * (size_t)r->G);
 }
 
 extern "C" void scc_de_result_destroy(scc_de_result* r) { delete r; }

@@ -172,6 +172,7 @@ struct scc_de_result {
     const double *d_p = nullptr, *d_q = nullptr, *d_lfc = nullptr;
     const long long* d_u2 = nullptr;
     const uint8_t* d_de = nullptr;
+    const long long* d_t = nullptr;  // [K][G] tie terms (an scc_de_markers result only)
     bool vectors = true;  // d_p / d_lfc / d_u2 hold the [P][G] vectors (a FAST group-pair run: test_all only)
 };
 

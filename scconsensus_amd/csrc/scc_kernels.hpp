@@ -48,6 +48,7 @@ struct ScStatsLaunch {
     double* m2_pos;     // sum((x - mean_pos)^2), second pass
     double* min_pos;    // their minimum (+Inf when there is none)
     double* max_pos;    // their maximum (-Inf when there is none)
+    dd* sum_e;          // [K][G] the undivided double-double sums of expm1(x) (one-vs-rest only; else nullptr)
 };
 
 // one unit of rank work: a whole gene (src 0: the ingest's cluster-grouped
@@ -139,6 +140,46 @@ struct ScTestLaunch {
     const double* wtab;
     const int* woff;
     double* out_p;
+    double* out_lfc;
+    double* out_pct1;
+    double* out_pct2;
+    long long* out_u2;
+    long long* out_t;
+    uint8_t* out_flags;
+};
+
+// ---- one-vs-rest (scc_de_markers): cluster a against every other kept cell ----
+// The rank kernel (scc_rank_rest.hip) sorts a gene's nonzeros once and leaves
+//   R2[a][g] = sum over the nonzeros i of cluster a of (2 below(i) + n_t(i)),
+//   T[g]     = sum over the tie groups of the nonzeros of (n_t^3 - n_t),
+// below(i) the nonzeros of ANY cluster strictly below x_i, n_t(i) the size of
+// i's tie group.  Twice the midrank sum of cluster a among the nonzeros is
+// R2 + nz_a, so 2 (S_a) + E_a = R2 - nz_a^2 (k_rest_test adds the zero group).
+struct ScRestRankLaunch {
+    const long long* gstart;
+    const unsigned long long* keys;
+    int G, K, all;              // all: every gene is ranked (test_all)
+    const uint32_t* coff;
+    const int* cl_cc;
+    const uint8_t* flags;       // [K][G] bit0: cluster a tests the gene
+    unsigned long long* keys2;  // [nnz] sorted chunks of genes longer than one LDS chunk
+    uint8_t* codes2;            // [nnz]
+    unsigned long long* accR;   // [K][G]
+    unsigned long long* accT;   // [G]
+};
+
+struct ScRestTestLaunch {
+    int K, G, only_pos, all;
+    double min_pct, lfc_thr;
+    const int* n_clu;
+    const dd* sum_e;            // [K][G] (ScStatsLaunch::sum_e)
+    const uint32_t* cnt_pos;
+    const uint32_t* cnt_neg;
+    const unsigned long long* accR;
+    const unsigned long long* accT;
+    const double* wtab;
+    const int* woff;
+    double* out_p;              // all [K][G]
     double* out_lfc;
     double* out_pct1;
     double* out_pct2;
@@ -257,6 +298,9 @@ hipError_t scc_launch_rank_resplit(const ScRankLaunch* L, int grid, hipStream_t 
                                    int nside = 0, hipEvent_t fork = nullptr, const hipEvent_t* join = nullptr);
 hipError_t scc_launch_rank_cross_seg(const ScRankLaunch* L, int grid, hipStream_t st);
 hipError_t scc_launch_pair_filter(const ScTestLaunch* L, hipStream_t st);
+hipError_t scc_launch_rest_filter(const ScRestTestLaunch* L, hipStream_t st);
+hipError_t scc_launch_rest_test(const ScRestTestLaunch* L, hipStream_t st);
+hipError_t scc_launch_rank_rest(const ScRestRankLaunch* L, hipStream_t st);
 size_t scc_eigen_scratch_doubles(int n, int lda, int k);
 hipError_t scc_launch_eigen_topk(const double* A, int n, int lda, int k, double* scratch, double* Z, double* W,
                                  unsigned int** err_dev, int* nwg_out, hipEvent_t* marks,

@@ -128,7 +128,7 @@ __device__ inline double f64_wave_ext_dpp(double x)
 static_assert(sizeof(int) * (SCC_MAX_K + 1) + (sizeof(StatItem) + sizeof(StatMinMax)) * ST_NITEM <= 16 * 1024,
               "k_gene_stats: static LDS (off[], item[], mm[]) beyond 16 KiB a workgroup");
 
-template <bool EXPM1, bool SUMX, bool VAR, bool POS = false>
+template <bool EXPM1, bool SUMX, bool VAR, bool POS = false, bool SUME = false>
 __global__ void __launch_bounds__(ST_T) k_gene_stats(ScStatsLaunch A)
 {
     __shared__ int off[SCC_MAX_K + 1];
@@ -230,6 +230,7 @@ __global__ void __launch_bounds__(ST_T) k_gene_stats(ScStatsLaunch A)
             return;
         }
         if (EXPM1) A.mean_e[(size_t)a * A.G + g] = dd_div_n(se, na);
+        if (SUME) A.sum_e[(size_t)a * A.G + g] = se;  // one-vs-rest (an instance of its own): the rest's mean divides a sum of these
         if (SUMX) A.mean_x[(size_t)a * A.G + g] = dd_div_n(sx, na);
         A.cnt_pos[(size_t)a * A.G + g] = pos;
         A.cnt_neg[(size_t)a * A.G + g] = neg;
@@ -246,6 +247,8 @@ extern "C" hipError_t scc_launch_gene_stats(const ScStatsLaunch* L, hipStream_t 
     } else if (L->mode == SCC_DE_FAST && L->test == SCC_TEST_T) {
         hipLaunchKernelGGL((k_gene_stats<true, true, false>), grid, dim3(ST_T), 0, st, *L);
         hipLaunchKernelGGL((k_gene_stats<false, false, true>), grid, dim3(ST_T), 0, st, *L);
+    } else if (L->mode == SCC_DE_FAST && L->sum_e) {
+        hipLaunchKernelGGL((k_gene_stats<true, false, false, false, true>), grid, dim3(ST_T), 0, st, *L);
     } else if (L->mode == SCC_DE_FAST) {
         hipLaunchKernelGGL((k_gene_stats<true, false, false>), grid, dim3(ST_T), 0, st, *L);
     } else {

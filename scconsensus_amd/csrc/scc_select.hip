@@ -5,6 +5,9 @@
 //  k_pair_test      per (pair, gene): Fast feature filters (Fast:229-291) or
 //                   slow mean-diff + expression gate (slow:104-113), and the
 //                   wilcox.test p-value (exact / normal rule) from exact 2U, T.
+//  k_rest_filter / k_rest_test   the same two steps per (cluster, gene) for the
+//                   one-vs-rest run (scc_de_markers): cluster a against the
+//                   other kept cells, from the K-fold rank sums of k_rank_rest.
 //  k_pair_select    per pair: R's row order order(p, -avg_logFC) (Fast:346),
 //                   BH (Fast:347 lazy n / slow:116-121 n = G), q filter and
 //                   the dim > 1 rule (Fast:376-378), top_n with ties
@@ -377,6 +380,94 @@ __global__ void __launch_bounds__(256) k_pair_test(ScTestLaunch A)
     A.out_u2[pg] = (i64)u2;
     A.out_t[pg] = (i64)t;
     A.out_flags[pg] = (u8)(fl | (ex << 2));
+}
+
+// -------------------------------------------------------- per (cluster, gene): one-vs-rest
+// cells.1 = cluster a, cells.2 = every other kept cell (scc_de_markers).  The
+// rest's counts are the selection's minus cluster a's (integers: exact); its
+// mean of expm1(x) is the double-double sum of the other clusters' sums, added
+// in cluster order and divided once by n_rest -- never a total minus a part,
+// never a combination of rounded means.
+struct RestCell {
+    int na, nrest;
+    u64 pos_a, neg_a, pos_r, neg_r;
+};
+
+__device__ inline RestCell rest_cell(const ScRestTestLaunch& A, int a, int g)
+{
+    RestCell c{};
+    int nsel = 0;
+    u64 pos = 0, neg = 0;
+    for (int b = 0; b < A.K; ++b) {
+        nsel += A.n_clu[b];
+        pos += A.cnt_pos[(size_t)b * A.G + g];
+        neg += A.cnt_neg[(size_t)b * A.G + g];
+    }
+    c.na = A.n_clu[a];
+    c.nrest = nsel - c.na;
+    c.pos_a = A.cnt_pos[(size_t)a * A.G + g];
+    c.neg_a = A.cnt_neg[(size_t)a * A.G + g];
+    c.pos_r = pos - c.pos_a;
+    c.neg_r = neg - c.neg_a;
+    return c;
+}
+
+// The feature filters of ComputePairWiseDE (Fast:229-291) for (cluster a, rest);
+// only_pos keeps avg_logFC > thr instead of |avg_logFC| > thr (FindAllMarkers'
+// only.pos).  flags bit0: cluster a tests the gene.
+__global__ void __launch_bounds__(256) k_rest_filter(ScRestTestLaunch A)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = blockIdx.y;
+    if (g >= A.G) return;
+    const size_t ag = (size_t)a * A.G + g;
+    const RestCell c = rest_cell(A, a, g);
+    const double pct1 = (100.0 * (double)c.pos_a) / (double)c.na;
+    const double pct2 = (100.0 * (double)c.pos_r) / (double)c.nrest;
+    dd sr{0.0, 0.0};
+    for (int b = 0; b < A.K; ++b)
+        if (b != a) sr = dd_add(sr, A.sum_e[(size_t)b * A.G + g]);
+    const double m1 = log(dd_div_n(A.sum_e[ag], (double)c.na) + 1.0);
+    const double m2 = log(dd_div_n(sr, (double)c.nrest) + 1.0);
+    const double lfc = m1 - m2;
+    const double amax = pct1 > pct2 ? pct1 : pct2;
+    const bool pass_pct = amax > A.min_pct;
+    const bool pass_expr = (expm1(m1) > 0.0) || (expm1(m2) > 0.0);        // Fast:275
+    const bool pass_fc = A.only_pos ? lfc > A.lfc_thr : fabs(lfc) > A.lfc_thr;  // Fast:282-286
+    A.out_pct1[ag] = pct1;
+    A.out_pct2[ag] = pct2;
+    A.out_lfc[ag] = lfc;
+    A.out_flags[ag] = (pass_pct && pass_expr && pass_fc) ? 1 : 0;
+}
+
+// After k_rank_rest: 2U of cluster a against the rest and the tie term of the
+// whole selection, the zero group in closed form, and wilcox.test's p.
+// Untested cells (test_all = 0) carry u2 = t = -1 and p = NaN.
+__global__ void __launch_bounds__(256) k_rest_test(ScRestTestLaunch A)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = blockIdx.y;
+    if (g >= A.G) return;
+    const size_t ag = (size_t)a * A.G + g;
+    const u8 fl = A.out_flags[ag];
+    if (!(fl & 1) && !A.all) {
+        A.out_p[ag] = __longlong_as_double(0x7ff8000000000000ll);
+        A.out_u2[ag] = -1;
+        A.out_t[ag] = -1;
+        return;
+    }
+    const RestCell c = rest_cell(A, a, g);
+    const u64 nz_a = c.pos_a + c.neg_a;
+    const u64 za = (u64)c.na - nz_a, zr = (u64)c.nrest - c.pos_r - c.neg_r;
+    // 2 S_a + E_a = R2 - nz_a^2 over the nonzeros (scc_rank_rest.hip), then the zeros
+    const u64 u2 = A.accR[ag] - nz_a * nz_a + 2 * (za * c.neg_r + c.pos_a * zr) + za * zr;
+    const u64 t = A.accT[g] + f_tie3(za + zr);
+    u8 ex = 0;
+    const double pv = wilcox_p((i64)u2, (i64)t, c.na, c.nrest, A.wtab, A.woff, &ex);
+    A.out_p[ag] = pv;
+    A.out_u2[ag] = (i64)u2;
+    A.out_t[ag] = (i64)t;
+    A.out_flags[ag] = (u8)(fl | (ex << 2));
 }
 
 // -------------------------------------------------------- per pair counts
@@ -823,6 +914,20 @@ extern "C" hipError_t scc_launch_pair_test(const ScTestLaunch* L, hipStream_t st
 {
     if (L->ghi <= L->glo) return hipSuccess;
     hipLaunchKernelGGL(k_pair_test, dim3((L->ghi - L->glo + 255) / 256, L->P), dim3(256), 0, st, *L);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t scc_launch_rest_filter(const ScRestTestLaunch* L, hipStream_t st)
+{
+    if (L->G <= 0 || L->K <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rest_filter, dim3((L->G + 255) / 256, L->K), dim3(256), 0, st, *L);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t scc_launch_rest_test(const ScRestTestLaunch* L, hipStream_t st)
+{
+    if (L->G <= 0 || L->K <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rest_test, dim3((L->G + 255) / 256, L->K), dim3(256), 0, st, *L);
     return hipGetLastError();
 }
 
