@@ -592,6 +592,13 @@ SCC_API int scc_diag_eig_last_path(void);
  * SCC_INGEST_FULL=1), 2 the lean transpose of a validated dataset, 3 the
  * regroup of the dataset's gene-major mirror. */
 SCC_API int scc_diag_ingest_last_path(void);
+/* What the calling thread's last calls took from the dataset's gene-major
+ * mirror beyond the ingest: bit 1 its last PCA gather (scc_distance,
+ * scc_de_distance, scc_pca_scores) filled the panel and the column means from
+ * the mirror.  Bit 0 is kept for a DE run whose statistics are computed in
+ * the regroup's workgroups: no such route exists (it measured no faster than
+ * the separate launch), so the bit is always 0. */
+SCC_API int scc_diag_mirror_last_uses(void);
 /* Nearest-neighbour scans (one row each; one pass over the centroids each) of
  * the context's last scc_hclust_ward_d2_dev or scc_hclust_ward_d2_scores, for
  * bandwidth figures; -1 without a context. */

@@ -473,8 +473,11 @@ static int ensure_mirror(scc_ctx* c, DePlan* pl, const DeBuffers& B)
     const int64_t nnz1 = pl->nnz1;
     hipStream_t s0 = c->s0;
     if (!ds->m_gptr) {
+        // (with its segment table: 4 B per gene and segment of SCC_MIRROR_SEG cells)
+        const size_t seg_n = (size_t)G * ((size_t)(N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG + 1);
         const size_t m_bytes = sizeof(long long) * ((size_t)G + 1) + sizeof(int) * (size_t)G +
-                               (sizeof(unsigned int) + sizeof(unsigned long long)) * (size_t)nnz1;
+                               (sizeof(unsigned int) + sizeof(unsigned long long)) * (size_t)nnz1 +
+                               sizeof(unsigned int) * seg_n;
         size_t mfree = 0, mtot = 0;
         bool room = hipMemGetInfo(&mfree, &mtot) == hipSuccess && m_bytes <= mfree / 4;
         (void)hipGetLastError();
@@ -484,7 +487,8 @@ static int ensure_mirror(scc_ctx* c, DePlan* pl, const DeBuffers& B)
             if (hipMalloc((void**)&ds->m_gptr, sizeof(long long) * ((size_t)G + 1)) != hipSuccess ||
                 hipMalloc((void**)&ds->m_order, sizeof(int) * (size_t)G) != hipSuccess ||
                 hipMalloc((void**)&ds->m_cell, sizeof(unsigned int) * (size_t)nnz1) != hipSuccess ||
-                hipMalloc((void**)&ds->m_key, sizeof(unsigned long long) * (size_t)nnz1) != hipSuccess) {
+                hipMalloc((void**)&ds->m_key, sizeof(unsigned long long) * (size_t)nnz1) != hipSuccess ||
+                hipMalloc((void**)&ds->m_seg, sizeof(unsigned int) * seg_n) != hipSuccess) {
                 (void)hipGetLastError();
                 mirror_free(ds);
             } else {
@@ -494,7 +498,7 @@ static int ensure_mirror(scc_ctx* c, DePlan* pl, const DeBuffers& B)
                     // (nc >= ceil(N / 32), the build's chunks: the run's count rows and scratch hold the build's)
                     Scope sc(c, "ingest_mirror_build", s0);
                     e = scc_launch_mirror_build(ds->d_indptr, ds->d_rows, ds->d_vals, nnz1, N, G, B.d_cnt, B.d_cscr,
-                                                B.d_scan, ds->m_gptr, ds->m_cell, ds->m_key, s0);
+                                                B.d_scan, ds->m_gptr, ds->m_cell, ds->m_key, ds->m_seg, s0);
                     // the genes by descending length: the regroup's dispatch order
                     if (e == hipSuccess)
                         e = hipMemcpyAsync(gp.data(), ds->m_gptr, sizeof(long long) * gp.size(),

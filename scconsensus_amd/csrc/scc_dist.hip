@@ -8,6 +8,8 @@
 // Kernels
 //   k_gather_*      X[U, ] -> Xc (N x nu_pad, row-major fp64, zero padded)
 //   k_colsum/center R colMeans (LDOUBLE sum restated as double-double) and centring
+//   k_mir_panel / k_mir_colsum  the same panel and column sums from the dataset's
+//                   gene-major mirror (the union genes' entries only)
 //   k_gram_f64      C = Xc^T Xc, fp64 MFMA (v_mfma_f64_16x16x4_f64), split over
 //                   cell chunks into slabs reduced in a fixed order (deterministic)
 //   k_scores        P = Xc V_k (N x 16, zero padded components)
@@ -18,6 +20,7 @@
 //                   LDS-pipelined FP32 MFMA (v_mfma_f32_32x32x2_f32) Gram with the
 //                   1 - r epilogue fused into coalesced packed-column stores.
 #include "scc_common.hpp"
+#include "scc_kernels.hpp"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1050,6 +1053,200 @@ extern "C" hipError_t scc_launch_center(double* Xc, int N, int nu, int ld, dd* p
 {
     const int rpc = (N + nchunk - 1) / nchunk;
     hipLaunchKernelGGL(k_colsum, dim3((ld + 255) / 256, nchunk), dim3(256), 0, st, Xc, N, ld, rpc, part);
+    hipLaunchKernelGGL(k_colmean, dim3((ld + 3) / 4), dim3(256), 0, st, part, nchunk, ld, N, mean);
+    if (apply) hipLaunchKernelGGL(k_center, dim3(4096), dim3(256), 0, st, Xc, N, nu, ld, mean);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------- panel from the mirror
+// The same panel from the dataset's gene-major mirror (scc_ingest.hip): only
+// the union genes' entries are read (12 B each), not every cell's column of
+// row indices.  One workgroup per (segment of SCC_MIRROR_SEG cells, tile of 64
+// union genes): the mirror's segment table gives each gene's entries of the
+// segment (at most SCC_MIRROR_SEG, ascending cells) without a search, a wave
+// streams them, MP_GB genes' loads in flight, into an LDS tile that was
+// cleared first, and the tile leaves as whole 512-B row segments: absent
+// entries, the padding columns [nu, ld) and the padding rows [N, Npad) are
+// the tile's zeros, so no memset and no second kernel.  Values are
+// scc_val_of(key): the stored bits.  The one difference from the CSC gather:
+// a stored -0.0 is not in the mirror (the build keeps vals != 0.0), so it
+// arrives as +0.0.
+#define MP_T 512
+#define MP_GT 64
+#define MP_LDR (MP_GT + 1)  // tile row stride in doubles (odd: a gene's column over the cells spreads over the banks)
+#define MP_GB 8             // genes whose entries a wave has in flight
+static_assert(SCC_MIRROR_SEG == 128, "k_mir_panel: a gene's entries of a segment are two per lane");
+static_assert(MP_GT % ((MP_T / 64) * MP_GB) == 0, "k_mir_panel: whole gene batches per wave");
+__global__ void __launch_bounds__(MP_T) k_mir_panel(const i64* __restrict__ gptr, const u32* __restrict__ mcell,
+                                                    const u64* __restrict__ mkey, const u32* __restrict__ mseg,
+                                                    int nseg, int ntile, const int* __restrict__ genes, int nu,
+                                                    int ld, int Npad, double* __restrict__ Xc)
+{
+    extern __shared__ __attribute__((aligned(16))) double tile[];  // [SCC_MIRROR_SEG][MP_LDR]
+    __shared__ i64 sb[MP_GT];  // the tile's genes: first entry of the segment, and how many
+    __shared__ int sn[MP_GT];
+    const int tid = threadIdx.x, lane = tid & 63, wv = scc_wave_id();
+    const int s = blockIdx.x / ntile, t = blockIdx.x % ntile;  // (a segment's tiles together: neighbouring row pieces)
+    const int c0 = s * SCC_MIRROR_SEG;
+    if (tid < MP_GT) {
+        const int u = t * MP_GT + tid;
+        i64 b = 0;
+        int n = 0;
+        if (u < nu) {
+            const int g = genes[u];  // checked by the host
+            const u32* sg = mseg + (size_t)g * (nseg + 1) + s;
+            const u32 e0 = sg[0], e1 = sg[1];
+            n = min((int)(e1 - e0), SCC_MIRROR_SEG);
+            b = n > 0 ? gptr[g] + (i64)e0 : 0;  // (an empty stretch reads entry 0: clamped loads below)
+        }
+        sb[tid] = b;
+        sn[tid] = n;
+    }
+    for (int i = tid; i < SCC_MIRROR_SEG * MP_LDR; i += MP_T) tile[i] = 0.0;
+    __syncthreads();
+    constexpr int GPW = MP_GT / (MP_T / 64);  // genes per wave
+    for (int j0 = wv * GPW; j0 < (wv + 1) * GPW; j0 += MP_GB) {
+        int n[MP_GB];
+        u32 cl[MP_GB][2];
+        u64 kk[MP_GB][2];
+        int nmax = 0;
+#pragma unroll
+        for (int q = 0; q < MP_GB; ++q) {
+            n[q] = sn[j0 + q];
+            nmax = max(nmax, n[q]);
+        }
+        if (nmax == 0) continue;  // (wave-uniform)
+#pragma unroll
+        for (int q = 0; q < MP_GB; ++q) {  // clamped unconditional loads, all in flight together
+            const i64 b = sb[j0 + q];
+            const int i = min(lane, max(n[q] - 1, 0));
+            cl[q][0] = mcell[b + i];
+            kk[q][0] = mkey[b + i];
+        }
+        if (nmax > 64) {
+#pragma unroll
+            for (int q = 0; q < MP_GB; ++q) {
+                const i64 b = sb[j0 + q];
+                const int i = min(lane + 64, max(n[q] - 1, 0));
+                cl[q][1] = mcell[b + i];
+                kk[q][1] = mkey[b + i];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < MP_GB; ++q) {
+            const u32 r = cl[q][0] - (u32)c0;
+            if (lane < n[q] && r < (u32)SCC_MIRROR_SEG) tile[r * MP_LDR + j0 + q] = scc_val_of(kk[q][0]);
+        }
+        if (nmax > 64) {
+#pragma unroll
+            for (int q = 0; q < MP_GB; ++q) {
+                const u32 r = cl[q][1] - (u32)c0;
+                if (lane + 64 < n[q] && r < (u32)SCC_MIRROR_SEG) tile[r * MP_LDR + j0 + q] = scc_val_of(kk[q][1]);
+            }
+        }
+    }
+    __syncthreads();
+    const int nr = min(SCC_MIRROR_SEG, Npad - c0);
+    double* out = Xc + (size_t)c0 * ld + (size_t)t * MP_GT + lane;
+    for (int r0 = wv; r0 < nr; r0 += 4 * (MP_T / 64)) {
+        double x[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = tile[min(r0 + q * (MP_T / 64), nr - 1) * MP_LDR + lane];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (r0 + q * (MP_T / 64) < nr) out[(size_t)(r0 + q * (MP_T / 64)) * ld] = x[q];
+    }
+}
+
+// first index i of [lo, hi) (at most SCC_MIRROR_SEG entries of one gene,
+// ascending cells, gene-relative) whose cell is >= target, hi if none: three
+// rounds of clamped probes (8 blocks of 16, 8 pairs, one) instead of seven
+// dependent steps.  cells: the gene's first entry (an empty stretch probes
+// the array's own start, whose first hi entries exist)
+__device__ inline u32 mir_lower_bound(const u32* __restrict__ mcell, i64 b, u32 lo, u32 hi, u32 target)
+{
+    static_assert(SCC_MIRROR_SEG == 128, "mir_lower_bound: 8 x 8 x 2 entries");
+    const u32* cells = mcell + (hi > lo ? b : 0);
+    const u32 last = max(hi, 1u) - 1u;
+    u32 pos = lo;
+#pragma unroll
+    for (int step = 16; step >= 2; step /= 8) {
+        u32 c[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c[k] = cells[min(pos + (u32)(step * (k + 1) - 1), last)];
+        u32 t = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t += (pos + (u32)(step * (k + 1) - 1) < hi && c[k] < target);
+        pos += t * (u32)step;
+    }
+    const u32 c = cells[min(pos, last)];
+    return min(pos + (u32)(pos < hi && c < target), hi);
+}
+
+// k_colsum's partials from the mirror: one lane per (union gene, chunk) folds
+// the gene's entries of the chunk's cells in ascending cell order.  The zeros
+// k_colsum adds in between are exact no-ops (dd_add_d(s, 0.0) == s), so every
+// part[chunk][u] has k_colsum's bits; empty chunks and u >= nu are zero.  A
+// wave holds 64 consecutive chunks of one gene, so its lanes read one stretch
+// of the gene's entries.  The chunk's first and last entry are found inside
+// the segments (the segment table) that hold the chunk's first cell and the
+// cell behind its last, both searches' probes in flight together.
+#define MC_U 16
+__global__ void __launch_bounds__(256) k_mir_colsum(const i64* __restrict__ gptr, const u32* __restrict__ mcell,
+                                                    const u64* __restrict__ mkey, const u32* __restrict__ mseg,
+                                                    int nseg, const int* __restrict__ genes, int nu, int ld, int N,
+                                                    int rows_per_chunk, int nchunk, dd* __restrict__ part)
+{
+    const i64 idx = (i64)blockIdx.x * 256 + threadIdx.x;
+    const int u = (int)(idx / nchunk), chunk = (int)(idx % nchunk);
+    if (u >= ld) return;
+    const i64 cl0 = (i64)chunk * rows_per_chunk;
+    const int c0 = (int)min(cl0, (i64)N), c1 = (int)min((i64)N, cl0 + rows_per_chunk);
+    dd s{0.0, 0.0};
+    if (u < nu && c0 < c1) {
+        const int g = genes[u];
+        const u32* sg = mseg + (size_t)g * (nseg + 1);
+        const i64 b = gptr[g];
+        const int s0 = c0 / SCC_MIRROR_SEG, s1 = min(c1 / SCC_MIRROR_SEG, nseg - 1);  // (c1 == nseg * SEG: none >= c1)
+        const u32 lo0 = sg[s0], hi0 = sg[s0 + 1], lo1 = sg[s1], hi1 = sg[s1 + 1];
+        const u32 i0 = mir_lower_bound(mcell, b, lo0, hi0, (u32)c0);
+        const u32 i1 = mir_lower_bound(mcell, b, lo1, hi1, (u32)c1);
+        const u64* key = mkey + b + i0;
+        const int n = i1 > i0 ? (int)(i1 - i0) : 0;
+        for (int i = 0; i < n; i += MC_U) {
+            double x[MC_U];
+#pragma unroll
+            for (int q = 0; q < MC_U; ++q) x[q] = scc_val_of(key[min(i + q, n - 1)]);
+#pragma unroll
+            for (int q = 0; q < MC_U; ++q) s = dd_add_d(s, i + q < n ? x[q] : 0.0);  // (past the end: +0)
+        }
+    }
+    part[(size_t)chunk * ld + u] = s;
+}
+
+extern "C" hipError_t scc_launch_gather_mirror(const i64* gptr, const u32* mcell, const u64* mkey, const u32* mseg,
+                                               int N, int Npad, const int* genes, int nu, int ld, double* Xc,
+                                               hipStream_t st)
+{
+    const int nseg = (N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG, ntile = ld / MP_GT;
+    const size_t lds = sizeof(double) * SCC_MIRROR_SEG * MP_LDR;
+    hipError_t e = scc_set_lds((const void*)k_mir_panel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mir_panel, dim3((unsigned)nseg * ntile), dim3(MP_T), lds, st, gptr, mcell, mkey, mseg, nseg,
+                       ntile, genes, nu, ld, Npad, Xc);
+    return hipGetLastError();
+}
+
+// scc_launch_center with k_colsum's pass over the panel replaced by the
+// mirror's entries (the same part[][], then k_colmean as it is)
+extern "C" hipError_t scc_launch_center_mirror(const i64* gptr, const u32* mcell, const u64* mkey, const u32* mseg,
+                                               double* Xc, int N, int nu, int ld, const int* genes, dd* part,
+                                               int nchunk, double* mean, int apply, hipStream_t st)
+{
+    const int rpc = (N + nchunk - 1) / nchunk, nseg = (N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG;
+    const i64 nthr = (i64)ld * nchunk;
+    hipLaunchKernelGGL(k_mir_colsum, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, gptr, mcell, mkey, mseg,
+                       nseg, genes, nu, ld, N, rpc, nchunk, part);
     hipLaunchKernelGGL(k_colmean, dim3((ld + 3) / 4), dim3(256), 0, st, part, nchunk, ld, N, mean);
     if (apply) hipLaunchKernelGGL(k_center, dim3(4096), dim3(256), 0, st, Xc, N, nu, ld, mean);
     return hipGetLastError();

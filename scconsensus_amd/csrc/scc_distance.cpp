@@ -357,11 +357,21 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
         d_genes = const_cast<int*>(t_dev_union);
     else if ((rc = genes_h2d(c, d_genes, genes, nu, s0)))
         return rc;
+    // a dataset with a gene-major mirror (built by an earlier FAST DE run,
+    // never here): the panel and its column sums from the union genes' entries
+    // alone; SCC_GATHER_MIRROR=0 keeps the CSC gather
+    // (a single device; the device list and the sharded PCA gather from the CSC)
+    const bool from_mirror =
+        !ds->dense && ds->m_gptr && ds->m_seg && c->peers.empty() && env_int("SCC_GATHER_MIRROR", 1) != 0;
+    g_mirror_last_uses = (g_mirror_last_uses & ~2) | (from_mirror ? 2 : 0);
     {
         Scope sc(c, "gather", s0);
-        // (the union map and the padding rows' clear included)
-        HIPCHK(c, scc_launch_gather(ds->d_indptr, ds->d_rows, ds->d_vals, ds->d_dense, G, N, Npad, d_umap, d_genes, nu,
-                                    ld, d_X, s0));
+        if (from_mirror)
+            HIPCHK(c, scc_launch_gather_mirror(ds->m_gptr, ds->m_cell, ds->m_key, ds->m_seg, N, Npad, d_genes, nu, ld,
+                                               d_X, s0));
+        else  // (the union map and the padding rows' clear included)
+            HIPCHK(c, scc_launch_gather(ds->d_indptr, ds->d_rows, ds->d_vals, ds->d_dense, G, N, Npad, d_umap, d_genes,
+                                        nu, ld, d_X, s0));
     }
     unsigned int* d_eig_err = nullptr;  // the hand-off's time-out flag, read back after the last launch
     if (metric == SCC_DIST_PCA_EUCLID) {
@@ -377,7 +387,11 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
         {
             Scope sc(c, "center", s0);
             // the means only: the Gram and the scores centre on the fly (SCC_CENTER_FUSED=0: a centring pass)
-            HIPCHK(c, scc_launch_center(d_X, N, nu, ld, (dd*)d_part, nchunk_mean, d_mean, fused ? 0 : 1, s0));
+            if (from_mirror)
+                HIPCHK(c, scc_launch_center_mirror(ds->m_gptr, ds->m_cell, ds->m_key, ds->m_seg, d_X, N, nu, ld,
+                                                   d_genes, (dd*)d_part, nchunk_mean, d_mean, fused ? 0 : 1, s0));
+            else
+                HIPCHK(c, scc_launch_center(d_X, N, nu, ld, (dd*)d_part, nchunk_mean, d_mean, fused ? 0 : 1, s0));
         }
         {
             Scope sc(c, "gram", s0);

@@ -1132,9 +1132,23 @@ __global__ void __launch_bounds__(MR_T) k_mir_regroup(const i64* __restrict__ gp
     }
 }
 
+// build, between the passes (cnt: the exclusive prefixes over the 32-cell
+// chunks, row nch the totals): seg[g][s] = entries of gene g in cells
+// < s * SCC_MIRROR_SEG, s in [0, nseg]: where a gene's entries of a cell
+// segment start, for the PCA panel and the column sums (scc_dist.hip)
+__global__ void __launch_bounds__(256) k_mir_segtab(const u32* __restrict__ cnt, int nch, int G, int nseg,
+                                                    u32* __restrict__ seg)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    for (int s = blockIdx.y; s <= nseg; s += gridDim.y)
+        seg[(size_t)g * (nseg + 1) + s] = cnt[(size_t)min(s * (SCC_MIRROR_SEG / MR_BC), nch) * G + g];
+}
+static_assert(SCC_MIRROR_SEG % MR_BC == 0, "a cell segment is whole build chunks");
+
 extern "C" hipError_t scc_launch_mirror_build(const i64* indptr, const int* rows, const double* vals, i64 nnz, int N,
                                               int G, u32* cnt, u32* colscan_scratch, i64* scan_scratch, i64* gptr,
-                                              u32* mcell, u64* mkey, hipStream_t st)
+                                              u32* mcell, u64* mkey, u32* mseg, hipStream_t st)
 {
     const int nch = (N + MR_BC - 1) / MR_BC;
     hipError_t e = hipMemsetAsync(cnt, 0, sizeof(u32) * (size_t)nch * G, st);
@@ -1147,6 +1161,11 @@ extern "C" hipError_t scc_launch_mirror_build(const i64* indptr, const int* rows
     if (e != hipSuccess) return e;
     e = scc_launch_scan(cnt + (size_t)nch * G, G, gptr, scan_scratch, gptr + G, st);
     if (e != hipSuccess) return e;
+    if (mseg) {  // (before the fill, which advances the count rows)
+        const int nseg = (N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG;
+        hipLaunchKernelGGL(k_mir_segtab, dim3((G + 255) / 256, std::min(nseg + 1, 1024)), dim3(256), 0, st, cnt, nch,
+                           G, nseg, mseg);
+    }
     hipLaunchKernelGGL(k_mir_fill, dim3((nch + 3) / 4), dim3(256), 0, st, indptr, rows, vals, N, G, cnt, gptr, mcell,
                        mkey);
     return hipGetLastError();

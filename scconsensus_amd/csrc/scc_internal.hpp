@@ -145,6 +145,9 @@ struct scc_dataset {
     mutable unsigned int* m_cell = nullptr;       // [nnz]
     mutable unsigned long long* m_key = nullptr;  // [nnz]
     mutable int* m_order = nullptr;               // [G]
+    // [G][ceil(N / SCC_MIRROR_SEG) + 1]: a gene's entries before each segment of
+    // SCC_MIRROR_SEG cells, for the PCA panel and its column sums (scc_dist.hip)
+    mutable unsigned int* m_seg = nullptr;
     // device list: the replica on each peer engine of the context (same order
     // as scc_ctx::peers), and the stored values per gene that balance the
     // gene row-blocks (computed on the first sharded run)
@@ -294,6 +297,8 @@ void mirror_free(const scc_dataset* d);
 // which ingest the calling thread's last DE run took (scc_diag_ingest_last_path;
 // per thread: a device-list run has one host thread per device)
 extern thread_local int g_ingest_last_path;
+// scc_diag_mirror_last_uses: bit 1 the thread's last PCA gather read the mirror
+extern thread_local int g_mirror_last_uses;
 
 // after a synchronisation: the eigensolver flag an earlier device-output
 // scc_distance (which returns without synchronising) left in h_flag

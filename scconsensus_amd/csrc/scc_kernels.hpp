@@ -251,9 +251,22 @@ int scc_scan_scratch_blocks(long long n);
 // column scan's and the scan's scratch as for a run of that many chunks),
 // then regrouped by cluster at every call (code: int8 per cell, -1 unkept;
 // total: kept entries per gene of [glo, ghi) for the scan behind gstart)
+// mseg [G][ceil(N / SCC_MIRROR_SEG) + 1] (or nullptr: none): a gene's entries
+// before each segment of SCC_MIRROR_SEG cells (the last column: all of them)
+#define SCC_MIRROR_SEG 128
 hipError_t scc_launch_mirror_build(const long long* indptr, const int* rows, const double* vals, long long nnz, int N,
                                    int G, uint32_t* cnt, uint32_t* colscan_scratch, long long* scan_scratch,
-                                   long long* gptr, uint32_t* mcell, unsigned long long* mkey, hipStream_t st);
+                                   long long* gptr, uint32_t* mcell, unsigned long long* mkey, uint32_t* mseg,
+                                   hipStream_t st);
+// the PCA panel and its column sums from the mirror (scc_dist.hip): what
+// scc_launch_gather and scc_launch_center give for the whole cell range of a
+// sparse dataset, read from the union genes' entries alone
+hipError_t scc_launch_gather_mirror(const long long* gptr, const uint32_t* mcell, const unsigned long long* mkey,
+                                    const uint32_t* mseg, int N, int Npad, const int* genes, int nu, int ld,
+                                    double* Xc, hipStream_t st);
+hipError_t scc_launch_center_mirror(const long long* gptr, const uint32_t* mcell, const unsigned long long* mkey,
+                                    const uint32_t* mseg, double* Xc, int N, int nu, int ld, const int* genes,
+                                    dd* part, int nchunk, double* mean, int apply, hipStream_t st);
 hipError_t scc_launch_mirror_total(const long long* gptr, const uint32_t* mcell, const signed char* code, int glo,
                                    int ghi, uint32_t* total, hipStream_t st);
 hipError_t scc_launch_mirror_regroup(const long long* gptr, const uint32_t* mcell, const unsigned long long* mkey,

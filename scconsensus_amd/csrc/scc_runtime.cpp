@@ -473,10 +473,12 @@ void scc_rt::mirror_free(const scc_dataset* d)
     hipFree(d->m_cell);
     hipFree(d->m_key);
     hipFree(d->m_order);
+    hipFree(d->m_seg);
     d->m_gptr = nullptr;
     d->m_cell = nullptr;
     d->m_key = nullptr;
     d->m_order = nullptr;
+    d->m_seg = nullptr;
 }
 
 // which ingest the calling thread's last DE run took: 0 none yet, 1 the full
@@ -484,6 +486,12 @@ void scc_rt::mirror_free(const scc_dataset* d)
 // transpose of a validated dataset, 3 the regroup of the dataset's mirror
 thread_local int scc_rt::g_ingest_last_path = 0;
 extern "C" SCC_API int scc_diag_ingest_last_path(void) { return g_ingest_last_path; }
+
+// what the calling thread's last calls read from the mirror: bit 1 the last PCA
+// gather (scc_distance, scc_pca_scores) filled its panel from the mirror; bit 0
+// (statistics in the regroup's workgroups) has no route and stays 0
+thread_local int scc_rt::g_mirror_last_uses = 0;
+extern "C" SCC_API int scc_diag_mirror_last_uses(void) { return g_mirror_last_uses; }
 
 extern "C" void scc_dataset_destroy(scc_dataset* d)
 {
