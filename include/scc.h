@@ -592,6 +592,13 @@ SCC_API int scc_diag_eig_last_path(void);
  * SCC_INGEST_FULL=1), 2 the lean transpose of a validated dataset, 3 the
  * regroup of the dataset's gene-major mirror. */
 SCC_API int scc_diag_ingest_last_path(void);
+/* Which rank route the calling thread's last DE run took: 0 no run yet, 2 the
+ * walk of the dataset's value order (a FAST Wilcoxon run at K <= 16 over the
+ * whole gene range on one device, on a dataset that holds the order;
+ * SCC_RANK_VORDER=0 turns it off), 1 every other run: the per-call value
+ * buckets, and the runs that rank nothing or rank elsewhere (SLOW, the t and
+ * bimod tests, gene shards, K > 16, scc_de_markers). */
+SCC_API int scc_diag_rank_last_route(void);
 /* What the calling thread's last calls took from the dataset's gene-major
  * mirror beyond the ingest: bit 1 its last PCA gather (scc_distance,
  * scc_de_distance, scc_pca_scores) filled the panel and the column means from

@@ -461,6 +461,68 @@ static int upload_tables(scc_ctx* c, const DeBuffers& B)
     return SCC_OK;
 }
 
+// the mirror's bytes (with its segment table: 4 B per gene and segment of SCC_MIRROR_SEG cells)
+static size_t mirror_bytes(int G, int N, int64_t nnz1)
+{
+    const size_t seg_n = (size_t)G * ((size_t)(N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG + 1);
+    return sizeof(long long) * ((size_t)G + 1) + sizeof(int) * (size_t)G +
+           (sizeof(unsigned int) + sizeof(unsigned long long)) * (size_t)nnz1 + sizeof(unsigned int) * seg_n;
+}
+
+// the value order's bytes: the sorted cells, the cut table's starts and the
+// cuts at their bound (two buckets in a row hold more than 64 entries)
+static size_t vorder_cut_bound(int G, int64_t nnz1) { return sizeof(unsigned int) * ((size_t)(2 * nnz1 / 65) + (size_t)G + 1); }
+static size_t vorder_bytes(int G, int64_t nnz1)
+{
+    return sizeof(unsigned int) * ((size_t)nnz1 + (size_t)G + 1) + vorder_cut_bound(G, nnz1);
+}
+
+// The value order of a mirrored dataset (scc_vorder.hip), built once under
+// its own timer when the mirror and the order together fit the mirror's
+// memory rule; else the mirror stays alone and the rank stage keeps its
+// per-call buckets.  SCC_RANK_VORDER=0 (read at each call) skips the build.
+static int ensure_vorder(scc_ctx* c, const DePlan* pl, const DeBuffers& B)
+{
+    const scc_dataset* ds = pl->ds;
+    const int G = pl->G, N = pl->N;
+    const int64_t nnz1 = pl->nnz1;
+    if (ds->m_vcell || !ds->m_gptr || G < 1 || env_int("SCC_RANK_VORDER", 1) == 0) return SCC_OK;
+    // (the mirror is allocated already: the free memory it took counts as free for the rule)
+    const size_t m_bytes = mirror_bytes(G, N, nnz1), both = m_bytes + vorder_bytes(G, nnz1);
+    size_t mfree = 0, mtot = 0;
+    bool room = hipMemGetInfo(&mfree, &mtot) == hipSuccess && both <= (mfree + m_bytes) / 4;
+    (void)hipGetLastError();
+    const char* mb = getenv("SCC_INGEST_MIRROR_MAX_BYTES");
+    if (mb && *mb && (double)both > atof(mb)) room = false;
+    if (!room) return SCC_OK;
+    if (hipMalloc((void**)&ds->m_vcell, sizeof(unsigned int) * (size_t)nnz1) != hipSuccess ||
+        hipMalloc((void**)&ds->m_vbk_ptr, sizeof(unsigned int) * ((size_t)G + 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        vorder_free(ds);
+        return SCC_OK;
+    }
+    hipError_t e;
+    {
+        Scope sc(c, "rank_vorder_build", c->s0);
+        // (the sort's scratch: the run's keys2 and keys, [nnz1] u64 each, not yet written by this run)
+        e = scc_launch_vorder_build(ds->m_gptr, G, ds->m_cell, ds->m_key, ds->m_vcell, ds->m_vbk_ptr, &ds->m_vbk,
+                                    &ds->m_vnbk, B.d_cnt, B.d_gstart, B.d_scan, vorder_cut_bound(G, nnz1),
+                                    B.d_keys2, nnz1, B.d_keys, sizeof(unsigned long long) * (size_t)nnz1, c->s0);
+    }
+    if (e == hipErrorOutOfMemory) {  // the sort's scratch or the cut table: no order
+        (void)hipGetLastError();
+        vorder_free(ds);
+        return SCC_OK;
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        vorder_free(ds);
+        return fail(c, SCC_ERR_HIP, std::string("value order build failed: ") + hipGetErrorString(e));
+    }
+    if (!ds->m_vbk) vorder_free(ds);
+    return SCC_OK;
+}
+
 // The dataset's gene-major mirror (FAST runs on a validated sparse dataset,
 // whole range and gene shards alike): built here once, under its own timer,
 // when it fits in a quarter of the free memory (the tile-start cache's
@@ -473,11 +535,8 @@ static int ensure_mirror(scc_ctx* c, DePlan* pl, const DeBuffers& B)
     const int64_t nnz1 = pl->nnz1;
     hipStream_t s0 = c->s0;
     if (!ds->m_gptr) {
-        // (with its segment table: 4 B per gene and segment of SCC_MIRROR_SEG cells)
         const size_t seg_n = (size_t)G * ((size_t)(N + SCC_MIRROR_SEG - 1) / SCC_MIRROR_SEG + 1);
-        const size_t m_bytes = sizeof(long long) * ((size_t)G + 1) + sizeof(int) * (size_t)G +
-                               (sizeof(unsigned int) + sizeof(unsigned long long)) * (size_t)nnz1 +
-                               sizeof(unsigned int) * seg_n;
+        const size_t m_bytes = mirror_bytes(G, N, nnz1);
         size_t mfree = 0, mtot = 0;
         bool room = hipMemGetInfo(&mfree, &mtot) == hipSuccess && m_bytes <= mfree / 4;
         (void)hipGetLastError();
@@ -523,6 +582,7 @@ static int ensure_mirror(scc_ctx* c, DePlan* pl, const DeBuffers& B)
     }
     if (!ds->m_gptr) return SCC_OK;
     pl->route = INGEST_MIRROR;
+    if (int rc = ensure_vorder(c, pl, B)) return rc;
     if (ds->d_tbnd) {  // the transpose's tile starts: not needed any more
         hipFree(ds->d_tbnd);
         ds->d_tbnd = nullptr;
@@ -702,6 +762,44 @@ static ScRankLaunch rank_launch(const DePlan& pl, const DeBuffers& B)
     return L;
 }
 
+static int rank_log(scc_ctx* c, hipStream_t s0, const int* d_counts);
+
+// The value-order route: a FAST Wilcoxon run over the whole gene range on one
+// device, on a dataset that holds the order (SCC_RANK_VORDER=0, read at each
+// call: the per-call buckets).  The route is a call's, never a gene's.
+static bool rank_vorder_route(const scc_ctx* c, const DePlan& pl)
+{
+    const scc_dataset* ds = pl.ds;
+    return ds->m_vcell && ds->m_vbk && ds->m_gptr && pl.route == INGEST_MIRROR && pl.fast && !pl.norank &&
+           !pl.markers && !pl.shard_stage && pl.glo == 0 && pl.ghi == pl.G && c->peers.empty() &&
+           ds->m_vnbk <= pl.bucket_cap && !pl.stamps && env_int("SCC_RANK_VORDER", 1) != 0;
+}
+
+// classify, the dataset's buckets into the wave list, the pair counts, the
+// cross terms: no split, no re-split, no LDS items, no fork to s1
+static int rank_stage_vorder(scc_ctx* c, const DePlan& pl, const DeBuffers& B, ScRankLaunch& L)
+{
+    int rc;
+    hipStream_t s0 = c->s0;
+    const scc_dataset* ds = pl.ds;
+    L.vcell = ds->m_vcell, L.vbk_ptr = ds->m_vbk_ptr, L.vbk = ds->m_vbk, L.vgptr = ds->m_gptr;
+    L.code8 = B.d_code8;
+    L.fatbk = nullptr;  // (no re-split parents: k_rank_cross_seg has nothing to add)
+    const int ncu = c->n_cu > 0 ? c->n_cu : 256;
+    HIPCHK(c, scc_launch_rank_classify(&L, s0));
+    HIPCHK(c, scc_launch_rank_vorder_list(&L, std::max(1, std::min((pl.G + 7) / 8, 1 << 20)), s0));  // (8 genes a workgroup)
+    if (L.dbg == 7) scc_rank_mfma_stamps(s0, 0);
+    // K <= 16: one launch (k_rank_mfma16<1, true>), no side stream; else the slot
+    // classes' and the matrix-core class's launches on s0 and the two side streams
+    const int rw_side = (pl.K > 16 && env_int("SCC_RW_STREAMS", 1) != 0 && L.dbg != 7) ? 2 : 0;
+    HIPCHK(c, scc_launch_rank_waves(&L, 8 * ncu, s0, c->sw, rw_side, c->ev_wfork, c->ev_wj));
+    if (L.dbg == 7) scc_rank_mfma_stamps(s0, 1);
+    HIPCHK(c, scc_launch_rank_cross(&L, 4 * ncu, s0));
+    if (env_int("SCC_RANK_LOG", 0) && (rc = rank_log(c, s0, B.d_counts))) return rc;
+    g_rank_last_route = 2;
+    return SCC_OK;
+}
+
 // the rank stage's work counters on the host (diagnostics; synchronises s0)
 static hipError_t read_counts(const int* d_counts, hipStream_t s0, int* h)
 {
@@ -796,6 +894,7 @@ static int rank_stage(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
     hipStream_t s0 = c->s0, s1 = c->s1;
     Scope sc(c, "gene_rank", s0);
     ScRankLaunch L = rank_launch(pl, B);
+    if (rank_vorder_route(c, pl)) return rank_stage_vorder(c, pl, B, L);
     if (pl.stamps && (rc = rank_stamps_begin(c, s0, B.st_buf, pl.item_cap, L))) return rc;
     HIPCHK(c, scc_launch_rank_classify(&L, s0));
     const int ncu = c->n_cu > 0 ? c->n_cu : 256;
@@ -1078,6 +1177,7 @@ static int de_run(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_
         if ((rc = upload_tables(c, B))) return rc;
         if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
         g_ingest_last_path = pl.route;
+        g_rank_last_route = 1;  // (rank_stage: 2 on the value-order route)
         if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
         if ((rc = gene_stats(c, pl, B))) return rc;
         if (!pl.fast && (rc = slow_threshold(c, pl, B, &pl.log_thr))) return rc;
@@ -1200,6 +1300,7 @@ extern "C" int scc_de_markers(scc_ctx* c, const scc_dataset* ds, const int32_t* 
     if ((rc = upload_tables(c, B))) return rc;
     if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
     g_ingest_last_path = pl.route;
+    g_rank_last_route = 1;
     if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
     if ((rc = gene_stats(c, pl, B))) return rc;
     const ScRestTestLaunch T = rest_launch(c, pl, B, mp->only_pos ? 1 : 0);

@@ -148,6 +148,16 @@ struct scc_dataset {
     // [G][ceil(N / SCC_MIRROR_SEG) + 1]: a gene's entries before each segment of
     // SCC_MIRROR_SEG cells, for the PCA panel and its column sums (scc_dist.hip)
     mutable unsigned int* m_seg = nullptr;
+    // the mirror's value order (scc_vorder.hip; 4 B per stored value and about
+    // 4 B per 50): each gene's cells in ascending key order, equal keys in cell
+    // order, bit 31 set where the key equals the previous entry's; and each
+    // gene's bucket cuts inside that order (<= 64 entries, whole tie groups;
+    // bit 31: one tie group of more than 64).  Built with the mirror when both
+    // fit its memory rule; freed with it.
+    mutable unsigned int* m_vcell = nullptr;    // [nnz]
+    mutable unsigned int* m_vbk_ptr = nullptr;  // [G + 1]
+    mutable unsigned int* m_vbk = nullptr;      // [m_vnbk]
+    mutable long long m_vnbk = 0;
     // device list: the replica on each peer engine of the context (same order
     // as scc_ctx::peers), and the stored values per gene that balance the
     // gene row-blocks (computed on the first sharded run)
@@ -293,10 +303,13 @@ void scc_enter(const scc_ctx* c);
 
 // frees a dataset's gene-major mirror (scc_runtime.cpp; the DE driver builds it)
 void mirror_free(const scc_dataset* d);
+void vorder_free(const scc_dataset* d);
 
 // which ingest the calling thread's last DE run took (scc_diag_ingest_last_path;
 // per thread: a device-list run has one host thread per device)
 extern thread_local int g_ingest_last_path;
+// which rank route it took (scc_diag_rank_last_route)
+extern thread_local int g_rank_last_route;
 // scc_diag_mirror_last_uses: bit 1 the thread's last PCA gather read the mirror
 extern thread_local int g_mirror_last_uses;
 

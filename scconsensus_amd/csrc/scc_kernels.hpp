@@ -112,6 +112,13 @@ struct ScRankLaunch {
     int tp_global;              // items' tested-pair tables in HBM (scc_rank_tables_global)
     char* tp_scr;               // [item workgroups][tp_scr_stride] when tp_global
     size_t tp_scr_stride;
+    // the value-order route (nullptr: today's buckets): the dataset's sorted cells
+    // and bucket cuts (scc_vorder.hip), the mirror's gene starts and the call's codes
+    const uint32_t* vcell;      // [nnz] cell | tie bit << 31
+    const uint32_t* vbk_ptr;    // [G + 1]
+    const uint32_t* vbk;        // bucket starts inside the gene's segment | fat bit << 31
+    const long long* vgptr;     // [G + 1] the mirror's gene starts
+    const signed char* code8;   // [N] cluster code of each cell, -1 unkept
 };
 
 
@@ -273,6 +280,18 @@ hipError_t scc_launch_mirror_regroup(const long long* gptr, const uint32_t* mcel
                                      const signed char* code, const int* order, int glo, int ghi, int K, int G,
                                      const int* cl_cc, const long long* gstart, uint32_t* cnt,
                                      unsigned long long* keys, hipStream_t st);
+// the mirror's value order (scc_vorder.hip): vcell [nnz] each gene's cells in
+// ascending key order (bit 31: the key equals the previous entry's), vbk_ptr
+// [G + 1] / vbk the genes' bucket cuts (positions in the sorted segment; bit
+// 31: one tie group of more than 64 entries).  cnt: [G], bptr: [G + 1], the
+// scan's scratch as for G.  *vbk_out is allocated with hipMalloc (the caller
+// frees it); left nullptr when the table would pass vbk_max_bytes.  ks_lent
+// [ks_n] and tmp_lent: scratch lent to the sort (nullptr: it allocates its own).
+hipError_t scc_launch_vorder_build(const long long* gptr, int G, const uint32_t* mcell, const unsigned long long* mkey,
+                                   uint32_t* vcell, uint32_t* vbk_ptr, uint32_t** vbk_out, long long* nbk_out,
+                                   uint32_t* cnt, long long* bptr, long long* scan_scratch, size_t vbk_max_bytes,
+                                   unsigned long long* ks_lent, long long ks_n, void* tmp_lent, size_t tmp_lent_bytes,
+                                   hipStream_t st);
 // CSR -> CSC transpose (scc_csr.hip): a plan sized on the host from (G, N,
 // nnz), one scratch blob, a validating pass, then the two-pass transpose
 struct ScCsrPlan {
@@ -300,6 +319,9 @@ int scc_rank_tables_global(int ntp_max, int K);
 size_t scc_rank_tables_stride(int ntp_max, int K);
 hipError_t scc_launch_rank_split(const ScRankLaunch* L, int grid, hipStream_t st);
 hipError_t scc_launch_rank_items(const ScRankLaunch* L, int cls, int grid, hipStream_t st);
+// the value-order route (L->vcell set): the classified genes' precomputed buckets
+// into the wave list; scc_launch_rank_waves then runs the VORD kernels over them
+hipError_t scc_launch_rank_vorder_list(const ScRankLaunch* L, int grid, hipStream_t st);
 // the slot classes' launches go round st, side[0], side[1], ... (nside 0: all
 // on st); a side stream is forked from st (event fork) when it first gets a
 // launch and joined back (its event in join[]) at the end

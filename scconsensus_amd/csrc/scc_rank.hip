@@ -977,6 +977,50 @@ static constexpr size_t kSplitStageOff = (sizeof(SplitLds) + 15) & ~(size_t)15;
 static_assert(kSplitStageOff + (size_t)SP_CHUNK * 9 <= 160 * 1024, "split LDS");
 
 
+// The tested pairs of gene g, compacted in pair order into gene_tp[g] as
+// p | a << 16 | b << 24, and their number (also gene_nt[g]).  A workgroup of
+// T threads; wsum: [T / 64] in LDS.
+template <int T>
+__device__ inline u32 gene_tested_pairs(const ScRankLaunch& A, int g, u32* wsum)
+{
+    const int K = A.K, G = A.G;
+    const int tid = threadIdx.x, lane = tid & 63, w = scc_wave_id();
+    u32 ntested = 0;
+    if constexpr (T == 64) {  // one wave (any wave of a workgroup, on a gene of its own): ballots alone
+        for (int p0 = 0; p0 < A.P; p0 += 64) {
+            const int p = p0 + lane;
+            const bool t = p < A.P && (A.all_pairs || (A.flags[(size_t)p * G + g] & 1));
+            const u64 bal = __ballot(t);
+            if (t) {
+                int a2, b2;
+                pair_decode(p, K, a2, b2);
+                A.gene_tp[(size_t)g * A.P + ntested + lanes_below(bal)] = (u32)p | ((u32)a2 << 16) | ((u32)b2 << 24);
+            }
+            ntested += (u32)__popcll(bal);
+        }
+        if (lane == 0) A.gene_nt[g] = (int)ntested;
+        return ntested;
+    }
+    for (int p0 = 0; p0 < A.P; p0 += T) {
+        const int p = p0 + tid;
+        const bool t = p < A.P && (A.all_pairs || (A.flags[(size_t)p * G + g] & 1));
+        const u64 bal = __ballot(t);
+        if (lane == 0) wsum[w] = (u32)__popcll(bal);
+        __syncthreads();
+        u32 o = ntested;
+        for (int v = 0; v < w; ++v) o += wsum[v];
+        if (t) {
+            int a2, b2;
+            pair_decode(p, K, a2, b2);
+            A.gene_tp[(size_t)g * A.P + o + lanes_below(bal)] = (u32)p | ((u32)a2 << 16) | ((u32)b2 << 24);
+        }
+        for (int v = 0; v < T / 64; ++v) ntested += wsum[v];
+        __syncthreads();
+    }
+    if (tid == 0) A.gene_nt[g] = (int)ntested;
+    return ntested;
+}
+
 // One ranked gene: 2048-bin histogram of its key window, bins packed into
 // value buckets of < 2 * target elements (a bin of more than `target` is a
 // bucket of its own), elements scattered into bucket order (keys2 / codes2
@@ -992,26 +1036,8 @@ __device__ void split_one_gene(const ScRankLaunch& A, int g, SplitLds& L)
     const u64* key = A.keys + base;
     if (tid <= K) L.off[tid] = (int)A.coff[(size_t)A.cl_cc[tid] * G + g];
     for (int i = tid; i < SP_BINS; i += SP_T) L.hist[i] = 0;
-    // tested pairs of the gene (the wave kernel holds at most 64 * A.rw_slots),
-    // compacted in pair order into gene_tp[g] as p | a << 16 | b << 24
-    u32 ntested = 0;
-    for (int p0 = 0; p0 < A.P; p0 += SP_T) {
-        const int p = p0 + tid;
-        const bool t = p < A.P && (A.all_pairs || (A.flags[(size_t)p * G + g] & 1));
-        const u64 bal = __ballot(t);
-        if (lane == 0) L.wsum2[w] = (u32)__popcll(bal);
-        __syncthreads();
-        u32 o = ntested;
-        for (int v = 0; v < w; ++v) o += L.wsum2[v];
-        if (t) {
-            int a2, b2;
-            pair_decode(p, K, a2, b2);
-            A.gene_tp[(size_t)g * A.P + o + lanes_below(bal)] = (u32)p | ((u32)a2 << 16) | ((u32)b2 << 24);
-        }
-        for (int v = 0; v < SP_W; ++v) ntested += L.wsum2[v];
-        __syncthreads();
-    }
-    if (tid == 0) A.gene_nt[g] = (int)ntested;
+    // tested pairs of the gene (the wave kernel holds at most 64 * A.rw_slots)
+    const u32 ntested = gene_tested_pairs<SP_T>(A, g, L.wsum2);
     const bool waves_ok = ntested <= (A.rw_slots >= RW_SLOTS_MAX ? (u32)RW_PAIRS_MAX : 64u * (u32)A.rw_slots);
     // the gene's keys stay in registers when they fit (SP_KPT per thread);
     // larger genes re-read each chunk in every pass (from L2)
@@ -2200,7 +2226,11 @@ __device__ inline void bitonic_merge(u64& key, u32& code, bool up, int lane)
     if constexpr (ST > 1) bitonic_merge<ST / 2>(key, code, up, lane);
 }
 
-template <int RW_SLOTS>
+// VORD: the buckets are the dataset's precomputed cuts of each gene's value
+// order, read through the call's cell codes (see k_rank_mfma16: unkept lanes
+// carry code 255 and are in no cluster mask; a bucket without a tie bit is
+// not sorted, one with a tie bit sorts (tie group, code) with the unkept last).
+template <int RW_SLOTS, bool VORD = false>
 __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
 {
     __shared__ u64 cms[4][SCC_MAX_K];  // per-wave cluster masks (K > 16)
@@ -2249,20 +2279,29 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
             return (i64)(((u64)(u32)__builtin_amdgcn_readlane((int)dhi, li) << 32) |
                          (u32)__builtin_amdgcn_readlane((int)dlo, li));
         };
+        // a bucket's first 64 elements (VORD: key = the vcell word, its tie bit in bit 31)
+        auto load = [&](i64 b, int nl, u64& k, u32& cd) {
+            if constexpr (VORD) {
+                const u32 w = lane < nl ? A.vcell[b + lane] : 0u;
+                const int c8 = lane < nl ? (int)A.code8[w & 0x7fffffffu] : -1;
+                k = (u64)w;
+                cd = c8 < 0 ? 255u : (u32)c8;
+            } else {
+                k = lane < nl ? A.keys2[b + lane] : ~0ull;
+                cd = lane < nl ? (u32)A.codes2[b + lane] : 255u;
+            }
+        };
         u64 nkey;
         u32 ncode;
         {
             const int l0 = __builtin_ctzll(rem);
-            const i64 b0 = dbase(l0);
-            const int n0 = __builtin_amdgcn_readlane(D.n, l0);
-            nkey = lane < n0 ? A.keys2[b0 + lane] : ~0ull;
-            ncode = lane < n0 ? (u32)A.codes2[b0 + lane] : 255u;
+            load(dbase(l0), __builtin_amdgcn_readlane(D.n, l0), nkey, ncode);
         }
         while (rem) {
             const int li = __builtin_ctzll(rem);
             rem &= rem - 1;
             const int g = __builtin_amdgcn_readlane(D.gene, li);
-            const int n = __builtin_amdgcn_readlane(D.n, li);
+            int n = __builtin_amdgcn_readlane(D.n, li);
             const int bucket = __builtin_amdgcn_readlane(D.bucket, li);
             const int src = __builtin_amdgcn_readlane(D.src, li);
             const i64 bbase = dbase(li);
@@ -2270,10 +2309,7 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
             u32 code = ncode;
             if (rem) {
                 const int l1 = __builtin_ctzll(rem);
-                const i64 b1 = dbase(l1);
-                const int n1 = __builtin_amdgcn_readlane(D.n, l1);
-                nkey = lane < n1 ? A.keys2[b1 + lane] : ~0ull;
-                ncode = lane < n1 ? (u32)A.codes2[b1 + lane] : 255u;
+                load(dbase(l1), __builtin_amdgcn_readlane(D.n, l1), nkey, ncode);
             }
             const bool big_ties = src == 2 && n > 2048;
             const u64 xadd = src == 2 ? (big_ties ? 0ull : (u64)n * n * n / 4 + 1) : 65536ull;
@@ -2296,7 +2332,7 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
             xbud += xadd;
             if (g != cur) {
                 cur = g;
-                gk = A.gkmin[g];
+                if constexpr (!VORD) gk = A.gkmin[g];
                 // tested pairs of g in pair order (compacted by the split)
                 // this launch's window of the gene's tested pairs (wv_base > 0: the
                 // second pass over a gene with more than 64 * RW_SLOTS of them)
@@ -2319,7 +2355,12 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int i = i0 + u * 64 + lane;
-                        cd[u] = i < n ? (u32)A.codes2[bbase + i] : 255u;
+                        if constexpr (VORD) {
+                            const int c8 = i < n ? (int)A.code8[A.vcell[bbase + i] & 0x7fffffffu] : -1;
+                            cd[u] = c8 < 0 ? 255u : (u32)c8;
+                        } else {
+                            cd[u] = i < n ? (u32)A.codes2[bbase + i] : 255u;
+                        }
                     }
                     for (int c = 0; c < K; ++c) {
                         u32 t = 0;
@@ -2365,8 +2406,31 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
                 continue;
             }
             // ---- load and bitonic sort by (key, code) across the lanes (invalid lanes last)
-            const bool vl = lane < n;
-            if (A.dbg == 2) {
+            bool vl = lane < n;
+            if constexpr (VORD) {
+                const u64 tb = __ballot(vl && ((key >> 31) & 1ull));
+                if (tb) {
+                    // (lane 0 of a bucket starts a group: its bit is clear, so a group number is >= 1)
+                    const u64 vm = (n >= 64) ? ~0ull : ((1ull << n) - 1);
+                    const u64 le = (lane == 63) ? ~0ull : ((2ull << lane) - 1);
+                    const u64 grp = (u64)__popcll(~tb & vm & le);
+                    const bool kept = vl && code != 255u;
+                    const int nk = __popcll(__ballot(kept));
+                    u64 ck = kept ? ((grp << SCC_CODE_BITS) | code) : ~0ull;
+                    if (n > 1) bitonic_merge_ck<1, 2>(ck);
+                    if (n > 2) bitonic_merge_ck<2, 4>(ck);
+                    if (n > 4) bitonic_merge_ck<4, 8>(ck);
+                    if (n > 8) bitonic_merge_ck<8, 16>(ck);
+                    if (n > 16) bitonic_merge_ck<16, 32>(ck);
+                    if (n > 32) bitonic_merge_ck<32, 0>(ck);
+                    n = nk;  // the kept elements, in (group, code) order in the first lanes
+                    vl = lane < n;
+                    key = ck >> SCC_CODE_BITS;
+                    code = vl ? (u32)(ck & SCC_CODE_MASK) : 255u;
+                } else {
+                    key = (u64)lane;  // every value its own group
+                }
+            } else if (A.dbg == 2) {
             } else if (gk != ~0ull) {  // one 64-bit sort key: (key - gene minimum) << 7 | cluster
                 u64 ck = vl ? (((key - gk) << SCC_CODE_BITS) | code) : ~0ull;
                 // levels up to the next power of two >= n (lanes past it hold only ~0)
@@ -2395,11 +2459,12 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
                     if (lane == c) cm = m;
                 }
             } else {  // many clusters: 7 ballots match equal codes, each cluster's leader posts its mask
-                const u64 peers = match_bits<SCC_CODE_BITS>(code & SCC_CODE_MASK, __ballot(vl));
+                const bool in_clu = vl && code != 255u;  // (VORD: an unkept lane inside the bucket)
+                const u64 peers = match_bits<SCC_CODE_BITS>(code & SCC_CODE_MASK, __ballot(in_clu));
                 cms[wv][lane] = 0;
                 if (K > 64) cms[wv][lane + 64] = 0;
                 wsync();
-                if (vl && lanes_below(peers) == 0) cms[wv][code] = peers;
+                if (in_clu && lanes_below(peers) == 0) cms[wv][code] = peers;
                 wsync();
                 cm = cms[wv][lane];
                 if (K > 64) cm1 = cms[wv][lane + 64];
@@ -2544,7 +2609,15 @@ __device__ constexpr int rk_tile16(int ma, int nb)  // upper tiles (ma <= nb) in
     return ma * NC - ma * (ma - 1) / 2 + (nb - ma);
 }
 
-template <int NC>
+// VORD: the buckets are the dataset's precomputed cuts of each gene's value
+// order (scc_vorder.hip): an element is a cell of A.vcell, its code the call's
+// code of that cell (unkept: 255, an all-zero one-hot row that adds nothing to
+// L O, O^T (2 M) or the histogram row, so unkept lanes stay where they are).
+// A bucket without a tie bit is in order as loaded: nothing is sorted.  With
+// one, the lanes' tie-group numbers stand for the keys: (group, code) is
+// sorted as the combined key is, unkept lanes last, because the tie terms
+// assume the codes in order inside a group.
+template <int NC, bool VORD = false>
 __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaunch A)  // NC >= 3: 2 waves / SIMD (NC = 4: 23 VGPRs spill)
 {
     constexpr int NTL = NC * (NC + 1) / 2;
@@ -2648,20 +2721,29 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                 return (i64)(((u64)(u32)__builtin_amdgcn_readlane((int)dhi, li) << 32) |
                              (u32)__builtin_amdgcn_readlane((int)dlo, li));
             };
+            // a bucket's first 64 elements (VORD: key = the vcell word, its tie bit in bit 31)
+            auto load = [&](i64 b, int nl, u64& k, u32& cd) {
+                if constexpr (VORD) {
+                    const u32 w = lane < nl ? A.vcell[b + lane] : 0u;
+                    const int c8 = lane < nl ? (int)A.code8[w & 0x7fffffffu] : -1;
+                    k = (u64)w;
+                    cd = c8 < 0 ? 255u : (u32)c8;
+                } else {
+                    k = lane < nl ? A.keys2[b + lane] : ~0ull;
+                    cd = lane < nl ? (u32)A.codes2[b + lane] : 255u;
+                }
+            };
             u64 nkey;
             u32 ncode;
             {
                 const int l0 = __builtin_ctzll(rem);
-                const i64 b0 = dbase(l0);
-                const int n0 = __builtin_amdgcn_readlane(D.n, l0);
-                nkey = lane < n0 ? A.keys2[b0 + lane] : ~0ull;
-                ncode = lane < n0 ? (u32)A.codes2[b0 + lane] : 255u;
+                load(dbase(l0), __builtin_amdgcn_readlane(D.n, l0), nkey, ncode);
             }
             while (rem) {
                 const int li = __builtin_ctzll(rem);
                 rem &= rem - 1;
                 const int g = __builtin_amdgcn_readlane(D.gene, li);
-                const int n = __builtin_amdgcn_readlane(D.n, li);
+                int n = __builtin_amdgcn_readlane(D.n, li);
                 const int bucket = __builtin_amdgcn_readlane(D.bucket, li);
                 const int src = __builtin_amdgcn_readlane(D.src, li);
                 const i64 bbase = dbase(li);
@@ -2669,16 +2751,13 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                 u32 code = ncode;
                 if (rem) {
                     const int l1 = __builtin_ctzll(rem);
-                    const i64 b1 = dbase(l1);
-                    const int n1 = __builtin_amdgcn_readlane(D.n, l1);
-                    nkey = lane < n1 ? A.keys2[b1 + lane] : ~0ull;
-                    ncode = lane < n1 ? (u32)A.codes2[b1 + lane] : 255u;
+                    load(dbase(l1), __builtin_amdgcn_readlane(D.n, l1), nkey, ncode);
                 }
                 if (g != cur || nrun >= 16384) {
                     if (cur >= 0) flush();
                     if (g != cur) {
                         cur = g;
-                        gk = A.gkmin[g];
+                        if constexpr (!VORD) gk = A.gkmin[g];
                         ntp = A.gene_nt[g];
                     }
                 }
@@ -2692,7 +2771,12 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int i = i00 + u * 64 + lane;
-                            cd[u] = i < n ? (u32)A.codes2[bbase + i] : 255u;
+                            if constexpr (VORD) {
+                                const int c8 = i < n ? (int)A.code8[A.vcell[bbase + i] & 0x7fffffffu] : -1;
+                                cd[u] = c8 < 0 ? 255u : (u32)c8;
+                            } else {
+                                cd[u] = i < n ? (u32)A.codes2[bbase + i] : 255u;
+                            }
                         }
                         for (int c = 0; c < K; ++c) {
                             u32 t = 0;
@@ -2722,8 +2806,31 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                     stamp(5);
                     continue;
                 }
-                const bool vl = lane < n;
-                if (gk != ~0ull) {
+                bool vl = lane < n;
+                if constexpr (VORD) {
+                    const u64 tb = __ballot(vl && ((key >> 31) & 1ull));
+                    if (tb) {
+                        // (lane 0 of a bucket starts a group: its bit is clear, so a group number is >= 1)
+                        const u64 vm = (n >= 64) ? ~0ull : ((1ull << n) - 1);
+                        const u64 le = (lane == 63) ? ~0ull : ((2ull << lane) - 1);
+                        const u64 grp = (u64)__popcll(~tb & vm & le);
+                        const bool kept = vl && code != 255u;
+                        const int nk = __popcll(__ballot(kept));
+                        u64 ck = kept ? ((grp << SCC_CODE_BITS) | code) : ~0ull;
+                        if (n > 1) bitonic_merge_ck<1, 2>(ck);
+                        if (n > 2) bitonic_merge_ck<2, 4>(ck);
+                        if (n > 4) bitonic_merge_ck<4, 8>(ck);
+                        if (n > 8) bitonic_merge_ck<8, 16>(ck);
+                        if (n > 16) bitonic_merge_ck<16, 32>(ck);
+                        if (n > 32) bitonic_merge_ck<32, 0>(ck);
+                        n = nk;  // the kept elements, in (group, code) order in the first lanes
+                        vl = lane < n;
+                        key = ck >> SCC_CODE_BITS;
+                        code = vl ? (u32)(ck & SCC_CODE_MASK) : 255u;
+                    } else {
+                        key = (u64)lane;  // every value its own group
+                    }
+                } else if (gk != ~0ull) {
                     u64 ck = vl ? (((key - gk) << SCC_CODE_BITS) | code) : ~0ull;
                     if (n > 1) bitonic_merge_ck<1, 2>(ck);
                     if (n > 2) bitonic_merge_ck<2, 4>(ck);
@@ -3132,7 +3239,8 @@ extern "C" hipError_t scc_launch_rank_waves(const ScRankLaunch* L, int grid, hip
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStreams& ss)
+template <bool VORD>
+static hipError_t rank_waves_launches_t(const ScRankLaunch* L, int grid, SideStreams& ss)
 {
     // the launches below touch disjoint genes' accumulator cells (each gene is
     // in one class) or, for the windows of one gene, disjoint pair rows, and
@@ -3169,13 +3277,13 @@ static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStrea
         st = place(4);
         M.wv_hi = 1 << 30;
         if (L->K <= 16)
-            hipLaunchKernelGGL(k_rank_mfma16<1>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<1, VORD>), dim3(grid), dim3(256), 0, st, M);
         else if (L->K <= 32)
-            hipLaunchKernelGGL(k_rank_mfma16<2>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<2, VORD>), dim3(grid), dim3(256), 0, st, M);
         else if (L->K <= 48)
-            hipLaunchKernelGGL(k_rank_mfma16<3>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<3, VORD>), dim3(grid), dim3(256), 0, st, M);
         else
-            hipLaunchKernelGGL(k_rank_mfma16<4>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<4, VORD>), dim3(grid), dim3(256), 0, st, M);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess || L->rw_mfma == 2) return e;
     }
@@ -3189,9 +3297,9 @@ static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStrea
         M.wv_lo = -1;
         M.wv_hi = mfma ? mfma_min : (1 << 30);
         if (L->K <= 16)
-            hipLaunchKernelGGL(k_rank_mfma16<1>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<1, VORD>), dim3(grid), dim3(256), 0, st, M);
         else
-            hipLaunchKernelGGL(k_rank_mfma16<2>, dim3(grid), dim3(256), 0, st, M);
+            hipLaunchKernelGGL((k_rank_mfma16<2, VORD>), dim3(grid), dim3(256), 0, st, M);
         return hipGetLastError();
     }
     for (int c = 0; c < 4; ++c) {
@@ -3203,13 +3311,13 @@ static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStrea
         A.wv_filter = L->rw_slots > 2 ? 1 : 0;  // rw_slots 2: class 0 is the only launch and holds every gene
         st = place(c);
         if (c == 0)
-            hipLaunchKernelGGL(k_rank_waves<2>, dim3(grid), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_rank_waves<2, VORD>), dim3(grid), dim3(256), 0, st, A);
         else if (c == 1)
-            hipLaunchKernelGGL(k_rank_waves<4>, dim3(grid), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_rank_waves<4, VORD>), dim3(grid), dim3(256), 0, st, A);
         else if (c == 2)
-            hipLaunchKernelGGL(k_rank_waves<8>, dim3(grid), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_rank_waves<8, VORD>), dim3(grid), dim3(256), 0, st, A);
         else
-            hipLaunchKernelGGL(k_rank_waves<RW_SLOTS_MAX>, dim3(grid), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_rank_waves<RW_SLOTS_MAX, VORD>), dim3(grid), dim3(256), 0, st, A);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -3224,12 +3332,83 @@ static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStrea
             A.wv_hi = RW_PAIRS_MAX;
             A.wv_base = k * per;
             A.wv_filter = 1;
-            hipLaunchKernelGGL(k_rank_waves<RW_SLOTS_MAX>, dim3(grid), dim3(256), 0, st, A);
+            hipLaunchKernelGGL((k_rank_waves<RW_SLOTS_MAX, VORD>), dim3(grid), dim3(256), 0, st, A);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
     }
     return hipSuccess;
+}
+
+// (a launch that carries the dataset's value order: the VORD kernels)
+static hipError_t rank_waves_launches(const ScRankLaunch* L, int grid, SideStreams& ss)
+{
+    return L->vcell ? rank_waves_launches_t<true>(L, grid, ss) : rank_waves_launches_t<false>(L, grid, ss);
+}
+
+// The value-order route's bucket list, in place of the split: each classified
+// gene's tested pairs, then one wave bucket per precomputed cut of its sorted
+// segment (base: an offset into vcell; src 2: one tie group of more than 64),
+// contiguous and in value order in sbuckets and hbg as k_rank_cross expects.
+// A workgroup takes VL_G consecutive classified genes: one global atomic
+// reserves their buckets' ids and list slots together (an atomic per gene, all
+// on one counter, queued behind each other: 46 us at config B), then each
+// wave takes genes of its own.
+#define VL_G 8
+__global__ void __launch_bounds__(256) k_rank_vorder_list(ScRankLaunch A)
+{
+    __shared__ int sg[VL_G], sq0[VL_G], snb[VL_G], sat[VL_G];
+    const int tid = threadIdx.x, lane = tid & 63, wv = scc_wave_id();
+    const int cnt = split_count(A), nbig = A.counts[SCC_CNT_STRIDE * (13)];
+    for (int i0 = blockIdx.x * VL_G; i0 < cnt; i0 += gridDim.x * VL_G) {
+        const int ng = min(VL_G, cnt - i0);
+        if (tid < ng) {
+            const int g = split_gene_at(A, nbig, i0 + tid);
+            const u32 q0 = A.vbk_ptr[g];
+            sg[tid] = g;
+            sq0[tid] = (int)q0;
+            snb[tid] = (int)(A.vbk_ptr[g + 1] - q0);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int tot = 0;
+            for (int j = 0; j < ng; ++j) {
+                sat[j] = tot;
+                tot += snb[j];
+            }
+            // (bucket ids and list slots run together on this route: one bucket, one slot)
+            const int at = atomicAdd(&A.counts[SCC_CNT_STRIDE * (4)], tot);
+            atomicAdd(&A.counts[SCC_CNT_STRIDE * (5)], tot);
+            for (int j = 0; j < ng; ++j) sat[j] += at;
+        }
+        __syncthreads();
+        for (int j = wv; j < ng; j += 4) {
+            const int g = sg[j], nb = snb[j], bk0 = sat[j];
+            const u32 q0 = (u32)sq0[j];
+            const i64 base = A.vgptr[g];
+            const int n = (int)(A.vgptr[g + 1] - base);
+            gene_tested_pairs<64>(A, g, nullptr);
+            if (lane == 0) {
+                A.gene_bk[2 * g] = bk0;
+                A.gene_bk[2 * g + 1] = nb;
+            }
+            for (int q = lane; q < nb; q += 64) {
+                const u32 w0 = A.vbk[q0 + q];
+                const int s = (int)(w0 & 0x7fffffffu);
+                const int e = q + 1 < nb ? (int)(A.vbk[q0 + q + 1] & 0x7fffffffu) : n;
+                if (bk0 + q < A.bucket_cap)
+                    A.sbuckets[bk0 + q] = ScRankItem{base + s, e - s, g, (w0 >> 31) ? 2 : 1, bk0 + q};
+            }
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" hipError_t scc_launch_rank_vorder_list(const ScRankLaunch* L, int grid, hipStream_t st)
+{
+    if (grid <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rank_vorder_list, dim3(grid), dim3(256), 0, st, *L);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t scc_launch_rank_cross(const ScRankLaunch* L, int grid, hipStream_t st)

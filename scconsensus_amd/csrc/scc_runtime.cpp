@@ -474,12 +474,32 @@ void scc_rt::mirror_free(const scc_dataset* d)
     hipFree(d->m_key);
     hipFree(d->m_order);
     hipFree(d->m_seg);
+    vorder_free(d);
     d->m_gptr = nullptr;
     d->m_cell = nullptr;
     d->m_key = nullptr;
     d->m_order = nullptr;
     d->m_seg = nullptr;
 }
+
+// the mirror's value order (freed wherever the mirror is)
+void scc_rt::vorder_free(const scc_dataset* d)
+{
+    hipFree(d->m_vcell);
+    hipFree(d->m_vbk_ptr);
+    hipFree(d->m_vbk);
+    d->m_vcell = nullptr;
+    d->m_vbk_ptr = nullptr;
+    d->m_vbk = nullptr;
+    d->m_vnbk = 0;
+}
+
+// which rank route the calling thread's last DE run took: 0 no run yet, 1 the
+// per-call value buckets (split, re-split, in-wave sort, LDS items; also every
+// run that ranks nothing or ranks elsewhere: SLOW, the t and bimod tests, gene
+// shards, the one-vs-rest run), 2 the walk of the dataset's value order
+thread_local int scc_rt::g_rank_last_route = 0;
+extern "C" SCC_API int scc_diag_rank_last_route(void) { return g_rank_last_route; }
 
 // which ingest the calling thread's last DE run took: 0 none yet, 1 the full
 // read (the validating call, SLOW, dense, SCC_INGEST_FULL), 2 the lean
