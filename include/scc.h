@@ -602,9 +602,10 @@ SCC_API int scc_diag_rank_last_route(void);
 /* What the calling thread's last calls took from the dataset's gene-major
  * mirror beyond the ingest: bit 1 its last PCA gather (scc_distance,
  * scc_de_distance, scc_pca_scores) filled the panel and the column means from
- * the mirror.  Bit 0 is kept for a DE run whose statistics are computed in
- * the regroup's workgroups: no such route exists (it measured no faster than
- * the separate launch), so the bit is always 0. */
+ * the mirror.  Bit 0: its last DE run took the per-cluster gene statistics
+ * from the mirror, without the regroup (a run on the value-order route, rank
+ * route 2, at K <= 36; SCC_STATS_MIRROR=0 turns it off).  The ingest path
+ * such a run reports stays 3. */
 SCC_API int scc_diag_mirror_last_uses(void);
 /* Nearest-neighbour scans (one row each; one pass over the centroids each) of
  * the context's last scc_hclust_ward_d2_dev or scc_hclust_ward_d2_scores, for

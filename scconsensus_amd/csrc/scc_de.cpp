@@ -89,6 +89,9 @@ struct DePlan {
     int fat_cap;
     IngestRoute route;  // without the mirror; ensure_mirror sets INGEST_MIRROR
     bool try_mirror;
+    // decided once per run, after ensure_mirror (de_run): the rank stage walks the
+    // dataset's value order; the statistics come from the mirror, no regroup
+    bool vorder, stats_mirror;
     double log_thr;  // SLOW (set by slow_threshold; a finish stage: the shard run's)
 };
 
@@ -614,8 +617,11 @@ static int ingest_mirror(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
         HIPCHK(c, scc_launch_mirror_total(ds->m_gptr, ds->m_cell, B.d_code8, glo, ghi, d_total, s0));
         HIPCHK(c, scc_launch_scan(d_total, G, B.d_gstart, B.d_scan, B.d_gstart + G, s0));
     }
-    HIPCHK(c, scc_launch_mirror_regroup(ds->m_gptr, ds->m_cell, ds->m_key, B.d_code8, whole ? ds->m_order : nullptr,
-                                        glo, ghi, K, G, B.d_clcc, gstart_run, B.d_cnt, B.d_keys, s0));
+    // (the value-order route reads neither the regrouped keys nor the offset rows, and k_mir_stats reads the mirror)
+    if (!pl.stats_mirror)
+        HIPCHK(c, scc_launch_mirror_regroup(ds->m_gptr, ds->m_cell, ds->m_key, B.d_code8,
+                                            whole ? ds->m_order : nullptr, glo, ghi, K, G, B.d_clcc, gstart_run,
+                                            B.d_cnt, B.d_keys, s0));
     return SCC_OK;
 }
 
@@ -677,6 +683,12 @@ static int ingest_transpose(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
 static int gene_stats(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
 {
     Scope sc(c, "gene_stats", c->s0);
+    if (pl.stats_mirror) {
+        const scc_dataset* ds = pl.ds;
+        HIPCHK(c, scc_launch_mirror_stats(ds->m_gptr, ds->m_cell, ds->m_key, B.d_code8, ds->m_order, pl.G, pl.K,
+                                          gene_starts(pl, B), B.d_nclu, B.d_me, B.d_cntpos, B.d_cntneg, c->s0));
+        return SCC_OK;
+    }
     ScStatsLaunch S{};
     S.gstart = gene_starts(pl, B);
     S.keys = B.d_keys;
@@ -766,13 +778,24 @@ static int rank_log(scc_ctx* c, hipStream_t s0, const int* d_counts);
 
 // The value-order route: a FAST Wilcoxon run over the whole gene range on one
 // device, on a dataset that holds the order (SCC_RANK_VORDER=0, read at each
-// call: the per-call buckets).  The route is a call's, never a gene's.
+// call: the per-call buckets).  The route is a call's, never a gene's; de_run
+// asks once, after ensure_mirror, and keeps the answer in the plan.
 static bool rank_vorder_route(const scc_ctx* c, const DePlan& pl)
 {
     const scc_dataset* ds = pl.ds;
     return ds->m_vcell && ds->m_vbk && ds->m_gptr && pl.route == INGEST_MIRROR && pl.fast && !pl.norank &&
            !pl.markers && !pl.shard_stage && pl.glo == 0 && pl.ghi == pl.G && c->peers.empty() &&
            ds->m_vnbk <= pl.bucket_cap && !pl.stamps && env_int("SCC_RANK_VORDER", 1) != 0;
+}
+
+// On that route the rank kernels read the mirror, the order and the call's
+// codes, so the regroup's only reader left is k_gene_stats: k_mir_stats gives
+// its three arrays from the mirror instead, up to the K its lane sums fit
+// (SCC_STATS_MIRROR=0, read at each call: regroup + k_gene_stats).
+static bool stats_mirror_route(const DePlan& pl)
+{
+    return pl.vorder && pl.test == SCC_TEST_WILCOX && pl.ds->m_order && pl.K <= scc_mirror_stats_max_k() &&
+           env_int("SCC_STATS_MIRROR", 1) != 0;
 }
 
 // classify, the dataset's buckets into the wave list, the pair counts, the
@@ -894,7 +917,7 @@ static int rank_stage(scc_ctx* c, const DePlan& pl, const DeBuffers& B)
     hipStream_t s0 = c->s0, s1 = c->s1;
     Scope sc(c, "gene_rank", s0);
     ScRankLaunch L = rank_launch(pl, B);
-    if (rank_vorder_route(c, pl)) return rank_stage_vorder(c, pl, B, L);
+    if (pl.vorder) return rank_stage_vorder(c, pl, B, L);
     if (pl.stamps && (rc = rank_stamps_begin(c, s0, B.st_buf, pl.item_cap, L))) return rc;
     HIPCHK(c, scc_launch_rank_classify(&L, s0));
     const int ncu = c->n_cu > 0 ? c->n_cu : 256;
@@ -1176,8 +1199,11 @@ static int de_run(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_
     } else {
         if ((rc = upload_tables(c, B))) return rc;
         if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
+        pl.vorder = rank_vorder_route(c, pl);
+        pl.stats_mirror = stats_mirror_route(pl);
         g_ingest_last_path = pl.route;
         g_rank_last_route = 1;  // (rank_stage: 2 on the value-order route)
+        g_mirror_last_uses = (g_mirror_last_uses & ~1) | (pl.stats_mirror ? 1 : 0);
         if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
         if ((rc = gene_stats(c, pl, B))) return rc;
         if (!pl.fast && (rc = slow_threshold(c, pl, B, &pl.log_thr))) return rc;
@@ -1301,6 +1327,7 @@ extern "C" int scc_de_markers(scc_ctx* c, const scc_dataset* ds, const int32_t* 
     if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
     g_ingest_last_path = pl.route;
     g_rank_last_route = 1;
+    g_mirror_last_uses &= ~1;  // (one-vs-rest: regroup + k_gene_stats)
     if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
     if ((rc = gene_stats(c, pl, B))) return rc;
     const ScRestTestLaunch T = rest_launch(c, pl, B, mp->only_pos ? 1 : 0);

@@ -1132,6 +1132,271 @@ __global__ void __launch_bounds__(MR_T) k_mir_regroup(const i64* __restrict__ gp
     }
 }
 
+// ------------------------------------------------- statistics from the mirror
+// The FAST Wilcoxon statistics of a run whose rank stage walks the dataset's
+// value order: nothing else reads the regrouped keys there, so the per-cluster
+// expm1 sums and sign counts are taken from the mirror's cell-ordered rows
+// directly, and the regroup and k_gene_stats are not launched.  The results
+// equal theirs bit for bit, which fixes the order of every addition:
+//   - rr, an entry's rank among the gene's kept entries of its cluster in
+//     ascending cell order, is its place in the regrouped stretch;
+//   - Lp = max(64, roundup64(ceil(n / SCC_STATS_WAVES))), n the gene's kept
+//     entries, is k_gene_stats' piece length; entry rr is in piece rr / Lp and
+//     was added by lane rr % 64, in ascending rr, to a sum that starts {0, 0};
+//   - a piece's 64 lane sums go through dd_wave_sum_dpp, the pieces of a
+//     cluster are added from {0, 0} in ascending order, dd_div_n last.
+// One workgroup per gene, chunks of MS_CH entries: every lane loads cell and
+// key and takes expm1 at once (full lanes, cell order); the ballot match and
+// the scan of the step counts are the regroup's and give each entry's rank
+// inside the chunk's stretch of its cluster; the expm1 values are staged in
+// LDS grouped by cluster; then wave a % MS_W walks cluster a's stretch in
+// 64-aligned rows of rr (a row may begin in one chunk and end in the next:
+// its lanes are disjoint), one dd_add_d a row.  The lane sums live across
+// chunks: in registers for K <= MS_KREG (four clusters a wave), else in
+// dynamic LDS [K][64].  A row that opens a piece first closes the one before.
+#define MS_T 256
+#define MS_CH 1024                 // 8 KB of staged values (2,048 measured slower: more registers, fewer waves)
+#define MS_PER (MS_CH / MS_T)
+#define MS_NS (MS_CH / 64)
+#define MS_TPR (MS_T / MS_NS)      // threads that clear a wc row
+#define MS_W (MS_T / 64)
+#define MS_KREG (4 * MS_W)
+// [K][64] dd of dynamic LDS beside 16 KB static: three workgroups a CU still fit at 36
+#define MS_KLDS 36
+static_assert(MS_KREG <= 16 && MS_KLDS <= 64, "k_mir_stats: 4 and 6 code bits in the match");
+
+// mr_match with the number of code bits known at compile time
+template <int NB>
+__device__ inline u64 ms_match(int a, bool act)
+{
+    u64 m = __ballot(act);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const bool bit = (a >> b) & 1;
+        const u64 bb = __ballot(bit);
+        m &= bit ? bb : ~bb;
+    }
+    return m;
+}
+
+// cluster a's stretch of the chunk: cn values from sval[c0s], the first one of rank rb
+// dd_wave_sum_dpp of four values at once: after the butterfly's first stage
+// lanes l and l ^ 32 hold the same sum, so each half goes on with one value,
+// and after the second each quarter; a quarter's lanes then add what the
+// same lanes of the whole butterfly add, in the same order.  Lanes [0, 16)
+// end with x[0]'s sum, [16, 32) with x[2]'s, [32, 48) x[1]'s, [48, 64) x[3]'s.
+__device__ inline dd ms_wave_sum4(const dd (&x)[4], int lane)
+{
+    const dd s0 = dd_add(x[0], dd_xor_lane<32>(x[0])), s1 = dd_add(x[1], dd_xor_lane<32>(x[1]));
+    const dd s2 = dd_add(x[2], dd_xor_lane<32>(x[2])), s3 = dd_add(x[3], dd_xor_lane<32>(x[3]));
+    const bool up = lane & 32;
+    dd m01{up ? s1.hi : s0.hi, up ? s1.lo : s0.lo}, m23{up ? s3.hi : s2.hi, up ? s3.lo : s2.lo};
+    m01 = dd_add(m01, dd_xor_lane<16>(m01));
+    m23 = dd_add(m23, dd_xor_lane<16>(m23));
+    const bool odd = lane & 16;
+    dd m{odd ? m23.hi : m01.hi, odd ? m23.lo : m01.lo};
+    m = dd_add(m, dd_xor_lane<8>(m));
+    m = dd_add(m, dd_xor_lane<4>(m));
+    m = dd_add(m, dd_xor_lane<2>(m));
+    return dd_add(m, dd_xor_lane<1>(m));
+}
+
+// (nxt: the next row that opens a piece; a row that began in the chunk before opened its piece there)
+__device__ inline void ms_walk(const double* sval, u32 c0s, u32 cn, u32 rb, u32 Lp, int lane, dd& acc, dd* tot,
+                               u32& nxt)
+{
+    for (u32 r0 = rb & ~63u; r0 < rb + cn; r0 += 64u) {
+        if (r0 == nxt) {  // (wave-uniform; every lane writes the same total)
+            const dd t = dd_add(*tot, dd_wave_sum_dpp(acc));
+            *tot = t;
+            acc = dd{0.0, 0.0};
+            nxt += Lp;
+        }
+        const u32 rr = r0 + (u32)lane;
+        if (rr >= rb && rr < rb + cn) acc = dd_add_d(acc, sval[c0s + (rr - rb)]);
+    }
+}
+
+template <bool REG>
+__global__ void __launch_bounds__(MS_T, 6) k_mir_stats(const i64* __restrict__ gptr, const u32* __restrict__ mcell,
+                                                    const u64* __restrict__ mkey,
+                                                    const signed char* __restrict__ code,
+                                                    const int* __restrict__ order, int K, int G,
+                                                    const i64* __restrict__ gstart, const int* __restrict__ n_clu,
+                                                    double* __restrict__ mean_e, u32* __restrict__ cnt_pos,
+                                                    u32* __restrict__ cnt_neg)
+{
+    __shared__ double sval[MS_CH];             // the chunk's expm1 values grouped by cluster
+    __shared__ u32 wc[MS_NS][SCC_MAX_K / 2];   // as in k_mir_regroup
+    __shared__ u32 cst[SCC_MAX_K + 1];         // the chunk's stretches in sval
+    __shared__ u32 rbase[SCC_MAX_K];           // entries of cluster a in earlier chunks
+    __shared__ u32 cneg[SCC_MAX_K];            // values < 0 (a stored value is never 0: the others are > 0)
+    __shared__ u32 snxt[SCC_MAX_K];            // !REG: ms_walk's nxt
+    __shared__ dd stot[SCC_MAX_K];             // the closed pieces' sum
+    extern __shared__ dd ms_acc[];             // !REG: [K][64] lane sums
+    const int tid = threadIdx.x, lane = tid & 63, wv = scc_wave_id();
+    const int g = order[blockIdx.x];
+    const i64 b = gptr[g];
+    const int n = (int)(gptr[g + 1] - b);
+    const int nk = (int)(gstart[g + 1] - gstart[g]);
+    const u32 Lp = (u32)max(64, (((nk + SCC_STATS_WAVES - 1) / SCC_STATS_WAVES) + 63) & ~63);
+    const u64 below = (1ull << lane) - 1ull;
+    if (tid < SCC_MAX_K) {
+        cneg[tid] = 0u;
+        snxt[tid] = Lp;
+        stot[tid] = dd{0.0, 0.0};
+    }
+    dd acc[MS_KREG / MS_W];
+    u32 nxt[MS_KREG / MS_W];
+#pragma unroll
+    for (int q = 0; q < MS_KREG / MS_W; ++q) acc[q] = dd{0.0, 0.0}, nxt[q] = Lp;
+    if (!REG)
+        for (int i = tid; i < K * 64; i += MS_T) ms_acc[i] = dd{0.0, 0.0};
+    unsigned short* const wc16 = (unsigned short*)&wc[0][0];  // [MS_NS][SCC_MAX_K]
+    const int kw = (K + 1) >> 1;
+    u32 run0 = 0u, run1 = 0u;  // wave 0, lane j: entries of clusters 2 j and 2 j + 1 in earlier chunks
+    static_assert(MS_T / 64 * MS_PER == MS_NS && MS_NS % 8 == 0, "k_mir_stats: a wc row per MS_TPR threads");
+    for (int c0 = 0; c0 < n; c0 += MS_CH) {
+        const int len = min(MS_CH, n - c0);
+        for (int q = tid % MS_TPR; q < kw; q += MS_TPR) wc[tid / MS_TPR][q] = 0u;
+        u32 cl[MS_PER];
+        u64 kk[MS_PER];
+#pragma unroll
+        for (int u = 0; u < MS_PER; ++u) {  // (past the end: the chunk's last entry, not used)
+            const int ic = min(wv * (64 * MS_PER) + u * 64 + lane, len - 1);
+            cl[u] = mcell[b + c0 + ic];
+            kk[u] = mkey[b + c0 + ic];
+        }
+        int aa[MS_PER];
+        u32 rk[MS_PER];
+        double ev[MS_PER];
+        u32 sgn = 0u;  // bit u: entry u's value is < 0
+#pragma unroll
+        for (int u = 0; u < MS_PER; ++u) {
+            const int i = wv * (64 * MS_PER) + u * 64 + lane;
+            const int a = (int)code[cl[u]];
+            const double x = scc_val_of(kk[u]);
+            aa[u] = i < len ? a : -1;
+            sgn |= (u32)(~kk[u] >> 63) << u;
+            ev[u] = expm1(x);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < MS_PER; ++u) {  // step wv * MS_PER + u of the chunk
+            const bool act = aa[u] >= 0;
+            const u64 m = ms_match<REG ? 4 : 6>(aa[u], act);
+            const u64 mn = __ballot(act && ((sgn >> u) & 1u));
+            rk[u] = (u32)__popcll(m & below);
+            if (act && rk[u] == 0u) wc16[(wv * MS_PER + u) * SCC_MAX_K + aa[u]] = (unsigned short)__popcll(m);
+            if (mn != 0ull && act && rk[u] == 0u) {  // (rare: a step with negative values)
+                const u32 nn = (u32)__popcll(m & mn);
+                if (nn) atomicAdd(&cneg[aa[u]], nn);
+            }
+        }
+        __syncthreads();
+        if (wv == 0) {  // the steps' counts -> their bases inside the stretch, the stretches by a scan (k_mir_regroup)
+            u32 sum = 0u;
+            if (lane < kw) {
+                for (int s0 = 0; s0 < MS_NS; s0 += 8) {
+                    u32 x[8];
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) x[s] = wc[s0 + s][lane];
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) {
+                        wc[s0 + s][lane] = sum;
+                        sum += x[s];
+                    }
+                }
+            }
+            const u32 v0 = sum & 0xffffu, v1 = sum >> 16;
+            u32 inc = v0 + v1;
+            for (int o = 1; o < 64; o <<= 1) {
+                const u32 y = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += y;
+            }
+            cst[2 * lane] = inc - v0 - v1;
+            cst[2 * lane + 1] = inc - v1;
+            if (lane == 63) cst[SCC_MAX_K] = inc;
+            rbase[2 * lane] = run0;
+            rbase[2 * lane + 1] = run1;
+            run0 += v0;
+            run1 += v1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < MS_PER; ++u)
+            if (aa[u] >= 0) {
+                const u32 slot = cst[aa[u]] + (u32)wc16[(wv * MS_PER + u) * SCC_MAX_K + aa[u]] + rk[u];
+                if (slot < (u32)MS_CH) sval[slot] = ev[u];
+            }
+        __syncthreads();
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < MS_KREG / MS_W; ++q) {
+                const int a = q * MS_W + wv;
+                if (a < K) {
+                    const u32 c0s = (u32)__builtin_amdgcn_readfirstlane((int)cst[a]);
+                    const u32 cn = (u32)__builtin_amdgcn_readfirstlane((int)cst[a + 1]) - c0s;
+                    const u32 rb = (u32)__builtin_amdgcn_readfirstlane((int)rbase[a]);
+                    if (cn) ms_walk(sval, c0s, cn, rb, Lp, lane, acc[q], &stot[a], nxt[q]);
+                }
+            }
+        } else {
+            for (int a = wv; a < K; a += MS_W) {
+                const u32 c0s = (u32)__builtin_amdgcn_readfirstlane((int)cst[a]);
+                const u32 cn = (u32)__builtin_amdgcn_readfirstlane((int)cst[a + 1]) - c0s;
+                const u32 rb = (u32)__builtin_amdgcn_readfirstlane((int)rbase[a]);
+                if (cn) {
+                    dd s = ms_acc[a * 64 + lane];
+                    u32 nx = (u32)__builtin_amdgcn_readfirstlane((int)snxt[a]);
+                    ms_walk(sval, c0s, cn, rb, Lp, lane, s, &stot[a], nx);
+                    ms_acc[a * 64 + lane] = s;
+                    snxt[a] = nx;  // (every lane the same value)
+                }
+            }
+        }
+        // (the next chunk's first barrier, before its counts and stretches are written, ends this chunk's reads)
+    }
+    __syncthreads();  // (a gene without entries: the zeroed counts)
+    // a cluster's last piece (none: {0, 0} + {0, 0} is {0, 0}, what k_gene_stats
+    // divides there), four clusters' butterflies at a time
+    for (int a0 = wv; a0 < K; a0 += MS_KREG) {
+        dd x[MS_KREG / MS_W];
+#pragma unroll
+        for (int q = 0; q < MS_KREG / MS_W; ++q) {
+            const int a = a0 + q * MS_W;
+            x[q] = REG ? acc[q] : (a < K ? ms_acc[a * 64 + lane] : dd{0.0, 0.0});
+        }
+        const dd m = ms_wave_sum4(x, lane);
+        const int a = a0 + MS_W * (((lane >> 5) & 1) | ((lane >> 3) & 2));  // (the lane's quarter: ms_wave_sum4)
+        if (a < K && (lane & 15) == 0) {
+            const dd t = dd_add(stot[a], m);
+            const u32 all = n > 0 ? rbase[a] + cst[a + 1] - cst[a] : 0u;  // (the last chunk's)
+            mean_e[(size_t)a * G + g] = dd_div_n(t, (double)n_clu[a]);
+            cnt_pos[(size_t)a * G + g] = all - cneg[a];
+            cnt_neg[(size_t)a * G + g] = cneg[a];
+        }
+    }
+}
+
+extern "C" int scc_mirror_stats_max_k(void) { return MS_KLDS; }
+
+extern "C" hipError_t scc_launch_mirror_stats(const i64* gptr, const u32* mcell, const u64* mkey,
+                                              const signed char* code, const int* order, int G, int K,
+                                              const i64* gstart, const int* n_clu, double* mean_e, u32* cnt_pos,
+                                              u32* cnt_neg, hipStream_t st)
+{
+    if (G <= 0) return hipSuccess;
+    if (K < 1 || K > MS_KLDS) return hipErrorInvalidValue;
+    if (K <= MS_KREG)
+        hipLaunchKernelGGL((k_mir_stats<true>), dim3(G), dim3(MS_T), 0, st, gptr, mcell, mkey, code, order, K, G,
+                           gstart, n_clu, mean_e, cnt_pos, cnt_neg);
+    else
+        hipLaunchKernelGGL((k_mir_stats<false>), dim3(G), dim3(MS_T), sizeof(dd) * 64 * (size_t)K, st, gptr, mcell,
+                           mkey, code, order, K, G, gstart, n_clu, mean_e, cnt_pos, cnt_neg);
+    return hipGetLastError();
+}
+
 // build, between the passes (cnt: the exclusive prefixes over the 32-cell
 // chunks, row nch the totals): seg[g][s] = entries of gene g in cells
 // < s * SCC_MIRROR_SEG, s in [0, nseg]: where a gene's entries of a cell

@@ -310,7 +310,8 @@ void vorder_free(const scc_dataset* d);
 extern thread_local int g_ingest_last_path;
 // which rank route it took (scc_diag_rank_last_route)
 extern thread_local int g_rank_last_route;
-// scc_diag_mirror_last_uses: bit 1 the thread's last PCA gather read the mirror
+// scc_diag_mirror_last_uses: bit 0 the thread's last DE run took its statistics from
+// the mirror (no regroup), bit 1 its last PCA gather read the mirror
 extern thread_local int g_mirror_last_uses;
 
 // after a synchronisation: the eigensolver flag an earlier device-output

@@ -280,6 +280,16 @@ hipError_t scc_launch_mirror_regroup(const long long* gptr, const uint32_t* mcel
                                      const signed char* code, const int* order, int glo, int ghi, int K, int G,
                                      const int* cl_cc, const long long* gstart, uint32_t* cnt,
                                      unsigned long long* keys, hipStream_t st);
+// FAST Wilcoxon statistics straight from the mirror (k_mir_stats): mean_e,
+// cnt_pos and cnt_neg [K][G] as k_gene_stats<true, false, false> gives them
+// after the regroup, bit for bit, for every gene in `order` [G]; K at most
+// scc_mirror_stats_max_k().  gstart [G + 1]: the genes' kept entries.
+#define SCC_STATS_WAVES 4  // waves of k_gene_stats: they set its piece length, which fixes the summation order
+int scc_mirror_stats_max_k(void);
+hipError_t scc_launch_mirror_stats(const long long* gptr, const uint32_t* mcell, const unsigned long long* mkey,
+                                   const signed char* code, const int* order, int G, int K, const long long* gstart,
+                                   const int* n_clu, double* mean_e, uint32_t* cnt_pos, uint32_t* cnt_neg,
+                                   hipStream_t st);
 // the mirror's value order (scc_vorder.hip): vcell [nnz] each gene's cells in
 // ascending key order (bit 31: the key equals the previous entry's), vbk_ptr
 // [G + 1] / vbk the genes' bucket cuts (positions in the sorted segment; bit

@@ -86,6 +86,7 @@ __device__ inline u64 match_bits(u32 d, u64 act)
 // ===================================================================== stats
 #define ST_T 256
 #define ST_W (ST_T / 64)
+static_assert(ST_W == SCC_STATS_WAVES, "k_mir_stats (scc_ingest.hip) repeats k_gene_stats' pieces");
 #ifndef ST_U
 #define ST_U 4
 #endif
