@@ -599,6 +599,12 @@ SCC_API int scc_diag_ingest_last_path(void);
  * buckets, and the runs that rank nothing or rank elsewhere (SLOW, the t and
  * bimod tests, gene shards, K > 16, scc_de_markers). */
 SCC_API int scc_diag_rank_last_route(void);
+/* Whether that run formed the cross-bucket term of the rank sums per run: 1 on
+ * rank route 2 at K <= 16 with the matrix-core bucket kernel as the call's only
+ * bucket kernel (one histogram row per run of a gene's buckets inside a chunk
+ * of the bucket list; SCC_RANK_RUNS=0 turns it off), 0 every other run: a row
+ * per bucket and the cross kernel over buckets. */
+SCC_API int scc_diag_rank_last_runs(void);
 /* What the calling thread's last calls took from the dataset's gene-major
  * mirror beyond the ingest: bit 1 its last PCA gather (scc_distance,
  * scc_de_distance, scc_pca_scores) filled the panel and the column means from

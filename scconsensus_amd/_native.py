@@ -53,7 +53,7 @@ EXPORTS = [
     "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
     "scc_gene_distance", "scc_hclust_complete", "scc_dendro_reorder", "scc_heatmap_raster",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
-    "scc_diag_ingest_last_path", "scc_diag_rank_last_route", "scc_diag_mirror_last_uses", "scc_diag_hclust_last_scans",
+    "scc_diag_ingest_last_path", "scc_diag_rank_last_route", "scc_diag_rank_last_runs", "scc_diag_mirror_last_uses", "scc_diag_hclust_last_scans",
     "scc_diag_small_syev_stamps", "scc_diag_pvalues",
 ]
 
@@ -171,6 +171,7 @@ def load():
         "scc_diag_eig_last_path": (ctypes.c_int, []),
         "scc_diag_ingest_last_path": (ctypes.c_int, []),
         "scc_diag_rank_last_route": (ctypes.c_int, []),
+        "scc_diag_rank_last_runs": (ctypes.c_int, []),
         "scc_diag_mirror_last_uses": (ctypes.c_int, []),
         "scc_diag_small_syev_stamps": (ctypes.c_int, [vp]),
         "scc_diag_pvalues": (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),

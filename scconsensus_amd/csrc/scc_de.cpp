@@ -92,6 +92,8 @@ struct DePlan {
     // decided once per run, after ensure_mirror (de_run): the rank stage walks the
     // dataset's value order; the statistics come from the mirror, no regroup
     bool vorder, stats_mirror;
+    // ... and forms the cross-bucket term per run (rank_runs_route)
+    bool rank_runs;
     double log_thr;  // SLOW (set by slow_threshold; a finish stage: the shard run's)
 };
 
@@ -788,6 +790,17 @@ static bool rank_vorder_route(const scc_ctx* c, const DePlan& pl)
            ds->m_vnbk <= pl.bucket_cap && !pl.stamps && env_int("SCC_RANK_VORDER", 1) != 0;
 }
 
+// On that route at K <= 16 one launch of k_rank_mfma16<1, true> takes every
+// bucket (the same conditions as rank_waves_launches_t's): it can add the
+// cross-bucket term inside each run itself and leave one histogram row per run
+// (SCC_RANK_RUNS=0: a row per bucket and k_rank_cross over buckets).
+static bool rank_runs_route(const DePlan& pl)
+{
+    const int mfma = env_int("SCC_RANK_MFMA", 1), mfma16 = env_int("SCC_RANK_MFMA16", -1);
+    return pl.vorder && pl.K <= 16 && (mfma == 2 || mfma16 != 0) && env_int("SCC_RW_DEBUG", 0) == 0 &&
+           env_int("SCC_RANK_RUNS", 1) != 0;
+}
+
 // On that route the rank kernels read the mirror, the order and the call's
 // codes, so the regroup's only reader left is k_gene_stats: k_mir_stats gives
 // its three arrays from the mirror instead, up to the K its lane sums fit
@@ -809,17 +822,22 @@ static int rank_stage_vorder(scc_ctx* c, const DePlan& pl, const DeBuffers& B, S
     L.code8 = B.d_code8;
     L.fatbk = nullptr;  // (no re-split parents: k_rank_cross_seg has nothing to add)
     const int ncu = c->n_cu > 0 ? c->n_cu : 256;
+    L.rank_runs = pl.rank_runs ? 1 : 0;
+    L.rk_grid = 8 * ncu;
+    // (the accumulators' bound: a test lowers it to drive the flush inside a run)
+    L.run_bound = (unsigned int)std::max(1, env_int("SCC_RANK_RUN_BOUND", 0x7fffffff));
     HIPCHK(c, scc_launch_rank_classify(&L, s0));
     HIPCHK(c, scc_launch_rank_vorder_list(&L, std::max(1, std::min((pl.G + 7) / 8, 1 << 20)), s0));  // (8 genes a workgroup)
     if (L.dbg == 7) scc_rank_mfma_stamps(s0, 0);
     // K <= 16: one launch (k_rank_mfma16<1, true>), no side stream; else the slot
     // classes' and the matrix-core class's launches on s0 and the two side streams
     const int rw_side = (pl.K > 16 && env_int("SCC_RW_STREAMS", 1) != 0 && L.dbg != 7) ? 2 : 0;
-    HIPCHK(c, scc_launch_rank_waves(&L, 8 * ncu, s0, c->sw, rw_side, c->ev_wfork, c->ev_wj));
+    HIPCHK(c, scc_launch_rank_waves(&L, L.rk_grid, s0, c->sw, rw_side, c->ev_wfork, c->ev_wj));
     if (L.dbg == 7) scc_rank_mfma_stamps(s0, 1);
     HIPCHK(c, scc_launch_rank_cross(&L, 4 * ncu, s0));
     if (env_int("SCC_RANK_LOG", 0) && (rc = rank_log(c, s0, B.d_counts))) return rc;
     g_rank_last_route = 2;
+    g_rank_last_runs = L.rank_runs;
     return SCC_OK;
 }
 
@@ -1200,9 +1218,11 @@ static int de_run(scc_ctx* c, const scc_dataset* ds, const int32_t* code, int32_
         if ((rc = upload_tables(c, B))) return rc;
         if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
         pl.vorder = rank_vorder_route(c, pl);
+        pl.rank_runs = rank_runs_route(pl);
         pl.stats_mirror = stats_mirror_route(pl);
         g_ingest_last_path = pl.route;
         g_rank_last_route = 1;  // (rank_stage: 2 on the value-order route)
+        g_rank_last_runs = 0;
         g_mirror_last_uses = (g_mirror_last_uses & ~1) | (pl.stats_mirror ? 1 : 0);
         if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
         if ((rc = gene_stats(c, pl, B))) return rc;
@@ -1327,6 +1347,7 @@ extern "C" int scc_de_markers(scc_ctx* c, const scc_dataset* ds, const int32_t* 
     if (pl.try_mirror && (rc = ensure_mirror(c, &pl, B))) return rc;
     g_ingest_last_path = pl.route;
     g_rank_last_route = 1;
+    g_rank_last_runs = 0;
     g_mirror_last_uses &= ~1;  // (one-vs-rest: regroup + k_gene_stats)
     if ((rc = pl.route == INGEST_MIRROR ? ingest_mirror(c, pl, B) : ingest_transpose(c, pl, B))) return rc;
     if ((rc = gene_stats(c, pl, B))) return rc;

@@ -310,6 +310,8 @@ void vorder_free(const scc_dataset* d);
 extern thread_local int g_ingest_last_path;
 // which rank route it took (scc_diag_rank_last_route)
 extern thread_local int g_rank_last_route;
+// whether its cross term came from run rows (scc_diag_rank_last_runs)
+extern thread_local int g_rank_last_runs;
 // scc_diag_mirror_last_uses: bit 0 the thread's last DE run took its statistics from
 // the mirror (no regroup), bit 1 its last PCA gather read the mirror
 extern thread_local int g_mirror_last_uses;

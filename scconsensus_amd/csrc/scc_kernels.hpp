@@ -119,6 +119,13 @@ struct ScRankLaunch {
     const uint32_t* vbk;        // bucket starts inside the gene's segment | fat bit << 31
     const long long* vgptr;     // [G + 1] the mirror's gene starts
     const signed char* code8;   // [N] cluster code of each cell, -1 unkept
+    // run rows (value-order route, one k_rank_mfma16<1, true> launch): the bucket
+    // kernel adds the cross term inside each run (a gene's buckets within one
+    // chunk of the list) and leaves one hbg row per run, at the run's first
+    // list slot; k_rank_cross_runs sums over those rows
+    int rank_runs;              // 1: run rows, 0: a row per bucket and k_rank_cross
+    int rk_grid;                // the bucket kernel's grid: both kernels derive the chunk from it (rk_chunk)
+    unsigned int run_bound;     // what a 32-bit accumulator may hold between flushes (tests lower it)
 };
 
 

@@ -2179,6 +2179,19 @@ __device__ inline void bitonic_merge_ck(u64& ck)
     if constexpr (ST > 1) bitonic_merge_ck<ST / 2, UPBIT>(ck);
 }
 
+// The same merge on 32-bit keys (the value-order route's (group, code) keys fit
+// 15 bits, unkept lanes ~0): a lane keeps the smaller (KM bit set) or the larger
+// of its own key and its partner's, which is what the compare, ballot and two
+// selects of the 64-bit form decide; about half its VALU instructions.
+template <int ST, int UPBIT>
+__device__ inline void bitonic_merge_ck32(u32& ck)
+{
+    const u32 o = scc_xor_lane<ST>(ck);
+    constexpr u64 KM = bitonic_km(ST, UPBIT);
+    ck = lane_select(KM, max(ck, o), min(ck, o));
+    if constexpr (ST > 1) bitonic_merge_ck32<ST / 2, UPBIT>(ck);
+}
+
 __device__ inline u64 shfl_u64(u64 v, int src)
 {
     const u32 lo = (u32)__shfl((int)(u32)v, src, 64), hi = (u32)__shfl((int)(u32)(v >> 32), src, 64);
@@ -2417,17 +2430,17 @@ __global__ void __launch_bounds__(256) k_rank_waves(ScRankLaunch A)
                     const u64 grp = (u64)__popcll(~tb & vm & le);
                     const bool kept = vl && code != 255u;
                     const int nk = __popcll(__ballot(kept));
-                    u64 ck = kept ? ((grp << SCC_CODE_BITS) | code) : ~0ull;
-                    if (n > 1) bitonic_merge_ck<1, 2>(ck);
-                    if (n > 2) bitonic_merge_ck<2, 4>(ck);
-                    if (n > 4) bitonic_merge_ck<4, 8>(ck);
-                    if (n > 8) bitonic_merge_ck<8, 16>(ck);
-                    if (n > 16) bitonic_merge_ck<16, 32>(ck);
-                    if (n > 32) bitonic_merge_ck<32, 0>(ck);
+                    u32 ck = kept ? (((u32)grp << SCC_CODE_BITS) | code) : ~0u;  // (grp <= 64: a 32-bit key)
+                    if (n > 1) bitonic_merge_ck32<1, 2>(ck);
+                    if (n > 2) bitonic_merge_ck32<2, 4>(ck);
+                    if (n > 4) bitonic_merge_ck32<4, 8>(ck);
+                    if (n > 8) bitonic_merge_ck32<8, 16>(ck);
+                    if (n > 16) bitonic_merge_ck32<16, 32>(ck);
+                    if (n > 32) bitonic_merge_ck32<32, 0>(ck);
                     n = nk;  // the kept elements, in (group, code) order in the first lanes
                     vl = lane < n;
-                    key = ck >> SCC_CODE_BITS;
-                    code = vl ? (u32)(ck & SCC_CODE_MASK) : 255u;
+                    key = (u64)(ck >> SCC_CODE_BITS);
+                    code = vl ? (ck & (u32)SCC_CODE_MASK) : 255u;
                 } else {
                     key = (u64)lane;  // every value its own group
                 }
@@ -2588,7 +2601,14 @@ struct RkWaveLds {
     u8 dcnt[64];  // D_i at their operand slots
     u32 cnt[64];  // a fat bin's cluster counts
     u64 F[64];    // within-cluster tie terms of the current gene, per cluster
+    u32 pre[64];  // RUNS: the run's prefix counts per cluster, for the 64-bit cross sums
 };
+
+// The chunk of the bucket list a wave of k_rank_mfma16 takes at a time: chunk c
+// is the list slots [c CH, (c + 1) CH).  cnt: the list's length (the count word
+// [4], capped), grid: that kernel's workgroups.  k_rank_cross_runs finds the
+// run rows with the same two numbers (ScRankLaunch::rk_grid).
+__device__ inline int rk_chunk(int cnt, int grid) { return max(16, min(512, cnt / (4 * (grid * 4)))); }
 
 // The products on 16 x 16 x 64 tiles (K <= 16 * NC): one MFMA covers a
 // bucket's 64 elements, a cluster tile is 4 accumulator registers, so the
@@ -2599,6 +2619,14 @@ struct RkWaveLds {
 // g = l >> 4), element e(g, t) = 16 (t >> 2) + 4 g + (t & 3): the row the
 // accumulator layout puts in register t & 3 of lane group g of row tile
 // t >> 2, so four packed accumulator tiles are the next product's operand.
+// Lane shuffles of the bucket loop with their addresses formed once (a
+// __shfl* forms its source lane and clamps it at every call: four VALU
+// instructions a shuffle in a kernel bound by VALU issue).
+// the value of the lane below (lane 0: 0), one DPP move
+__device__ inline u32 rk_lane_up1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }
+// the value of lane addr4 / 4
+__device__ inline u32 rk_lane_at(int addr4, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute(addr4, (int)v); }
+
 __device__ inline rk_v4i rk_mfma16(rk_v4i a, rk_v4i b, rk_v4i c)
 {
     return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
@@ -2618,7 +2646,20 @@ __device__ constexpr int rk_tile16(int ma, int nb)  // upper tiles (ma <= nb) in
 // one, the lanes' tie-group numbers stand for the keys: (group, code) is
 // sorted as the combined key is, unkept lanes last, because the tie terms
 // assume the codes in order inside a group.
-template <int NC, bool VORD = false>
+// RUNS (with VORD, this launch the call's only bucket kernel): a wave walks
+// consecutive buckets of a gene in value order, so inside its run (the gene's
+// buckets within the chunk) it adds the cross-bucket term itself: pre[b], the
+// b-elements of the run's earlier buckets, is kept per lane for column
+// r16 (+ 16 t), and each bucket adds 2 h[a] pre[b] to a tile that joins R at
+// the flush (u2 = 2 S + E, so the doubled cross sum belongs where the doubled
+// in-bucket sum is).  The run's
+// totals go to the hbg row of the run's first list slot, max(bk0, c CH), the
+// only rows written: k_rank_cross_runs adds what the runs owe each other.
+// A wave-uniform bound of what a tile entry may have received since the last
+// flush keeps the 32-bit accumulators below A.run_bound: the accumulators are
+// flushed when it would pass, pre runs on.  A bucket whose own term would pass
+// it (a run that holds a tie group of millions) adds it in 64 bits instead.
+template <int NC, bool VORD = false, bool RUNS = false>
 __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaunch A)  // NC >= 3: 2 waves / SIMD (NC = 4: 23 VGPRs spill)
 {
     constexpr int NTL = NC * (NC + 1) / 2;
@@ -2631,8 +2672,9 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
     const int NW = gridDim.x * 4, W = blockIdx.x * 4 + wv;
     const int cnt = min(A.counts[SCC_CNT_STRIDE * (4)], A.bucket_cap);
     const int K = A.K, G = A.G, P = A.P;
-    const int CH = max(16, min(512, cnt / (4 * NW)));
+    const int CH = rk_chunk(cnt, (int)gridDim.x);
     const int g4 = lane >> 4, r16 = lane & 15;
+    const int at16 = (lane ^ 16) << 2, at32 = (lane ^ 32) << 2, atrow = g4 << 4, atcol = r16 << 2;  // rk_lane_at addresses
     const rk_v4i zero = {0, 0, 0, 0};
     // L rows 16 mt + r16: bytes [e(g4, t) < i] (formed where used: held for the
     // whole kernel they were 16 registers of the 2-waves-per-SIMD budget at NC = 4)
@@ -2649,6 +2691,30 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
     int cur = -1, ntp = 0, nrun = 0;
     bool rtie = false;
     u64 gk = ~0ull;
+    // RUNS: the open run's prefix, its row, its chunk, its elements so far; the bound
+    u32 pre[NC];
+#pragma unroll
+    for (int t = 0; t < NC; ++t) pre[t] = 0;
+    // the cross term's own tiles, added to R at a flush (R lives in the matrix
+    // cores' accumulator registers: adding there each bucket read and wrote them
+    // back around every product, 264 us against 250 at config B)
+    rk_v4i Cx[RUNS ? NTL : 1];
+#pragma unroll
+    for (int t = 0; t < (RUNS ? NTL : 1); ++t) Cx[t] = zero;
+    int rrow = -1, rc0 = -1;
+    u32 npre = 0, bnd = 0;  // (a gene holds fewer than 2^31 entries; bnd <= blim < 2^31)
+    const u32 blim = min(A.run_bound, 0x7fffffffu);
+    auto end_run = [&]() {
+        if (rrow >= 0) {
+#pragma unroll
+            for (int t = 0; t < NC; ++t)
+                if (g4 == 0 && r16 + 16 * t < K) A.hbg[(size_t)rrow * K + r16 + 16 * t] = pre[t];
+        }
+#pragma unroll
+        for (int t = 0; t < NC; ++t) pre[t] = 0;
+        npre = 0;
+        rrow = -1;
+    };
     const bool stm = A.dbg == 7;  // SCC_RW_DEBUG=7: phase clocks into g_rk_stamps
     u64 tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = stm ? __builtin_amdgcn_s_memtime() : 0;
     auto stamp = [&](int ph) {
@@ -2692,6 +2758,13 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
             }
             wsync();
         };
+        if constexpr (RUNS) {
+#pragma unroll
+            for (int t = 0; t < NTL; ++t) {
+                R[t] += Cx[t];
+                Cx[t] = zero;
+            }
+        }
         out(R, (unsigned long long*)A.accE);
         if (rtie) {
             out(X, (unsigned long long*)A.accX);
@@ -2702,6 +2775,7 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
         }
         nrun = 0;
         rtie = false;
+        bnd = 0;
     };
     for (int c0 = W * CH; c0 < cnt; c0 += NW * CH) {
         const int c1 = min(cnt, c0 + CH);
@@ -2710,7 +2784,9 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
             ScRankItem D{0, 0, 0, 0, 0};
             if (lane < s1 - s0) D = A.sbuckets[s0 + lane];
             u64 rem;
-            if (A.wv_filter) {
+            if constexpr (RUNS) {  // (every slot, so that each run's row is written)
+                rem = __ballot(lane < s1 - s0);
+            } else if (A.wv_filter) {
                 const int ntg = (lane < s1 - s0 && D.n > 0) ? A.gene_nt[D.gene] : -1;
                 rem = __ballot(ntg > A.wv_lo && ntg <= A.wv_hi);
             } else {
@@ -2754,12 +2830,34 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                     const int l1 = __builtin_ctzll(rem);
                     load(dbase(l1), __builtin_amdgcn_readlane(D.n, l1), nkey, ncode);
                 }
+                const bool newrun = RUNS && (g != cur || c0 != rc0);
+                if (newrun) end_run();
                 if (g != cur || nrun >= 16384) {
                     if (cur >= 0) flush();
                     if (g != cur) {
                         cur = g;
                         if constexpr (!VORD) gk = A.gkmin[g];
                         ntp = A.gene_nt[g];
+                    }
+                }
+                bool wide = false;  // RUNS: this bucket's cross term in 64 bits
+                if constexpr (RUNS) {
+                    if (newrun) {
+                        // every slot is walked and a bucket's id is its slot: the run's
+                        // first bucket is at max(bk0, c0), where k_rank_cross_runs looks
+                        // (no load of gene_bk on the gene-change path)
+                        rrow = bucket;
+                        rc0 = c0;
+                    }
+                    if (src != 2) {
+                        // a tile entry gets at most 2 n^2 from the bucket itself and 2 n npre from the run
+                        // (n <= 64; the prefix below 2^24 keeps the products in the 24-bit multiplier)
+                        const u32 own = 2u * (u32)n * (u32)n;
+                        const u64 add64 = own + 2ull * (u64)n * npre;
+                        wide = add64 > blim || npre >= (1u << 24);
+                        const u32 add = wide ? own : (u32)add64;
+                        if (bnd + add > blim && bnd) flush();
+                        bnd += add;
                     }
                 }
                 ++nrun;
@@ -2787,21 +2885,35 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                         }
                     }
                     if (lane < K) {
-                        A.hbg[(size_t)bucket * K + lane] = myc;
+                        if constexpr (!RUNS) A.hbg[(size_t)bucket * K + lane] = myc;
                         if (myc >= 2) Lw.F[lane] += f_tie(myc);
                     }
                     rtie = true;
                     Lw.cnt[lane] = myc;
+                    if constexpr (RUNS) {
+#pragma unroll
+                        for (int t = 0; t < NC; ++t)
+                            if (g4 == 0) Lw.pre[r16 + 16 * t] = pre[t];
+                    }
                     wsync();
                     const u32* tl = A.gene_tp + (size_t)g * P;
                     for (int j = lane; j < ntp; j += 64) {
                         const u32 v = tl[j];
                         const u64 ca = Lw.cnt[(v >> 16) & 0xffu], cb = Lw.cnt[v >> 24];
+                        const size_t o = (size_t)(v & 0xffffu) * G + g;
                         if (ca && cb) {
-                            const size_t o = (size_t)(v & 0xffffu) * G + g;
                             atomicAdd((unsigned long long*)&A.accE[o], (unsigned long long)(ca * cb));
                             atomicAdd((unsigned long long*)&A.accX[o], (unsigned long long)(ca * cb * (ca + cb)));
                         }
+                        if constexpr (RUNS) {  // the group's a-elements above the run's earlier b-elements
+                            const u64 pb = Lw.pre[v >> 24];
+                            if (ca && pb) atomicAdd((unsigned long long*)&A.accS[o], (unsigned long long)(ca * pb));
+                        }
+                    }
+                    if constexpr (RUNS) {
+#pragma unroll
+                        for (int t = 0; t < NC; ++t) pre[t] += Lw.cnt[r16 + 16 * t];
+                        npre += (u32)n;
                     }
                     wsync();
                     stamp(5);
@@ -2817,17 +2929,18 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                         const u64 grp = (u64)__popcll(~tb & vm & le);
                         const bool kept = vl && code != 255u;
                         const int nk = __popcll(__ballot(kept));
-                        u64 ck = kept ? ((grp << SCC_CODE_BITS) | code) : ~0ull;
-                        if (n > 1) bitonic_merge_ck<1, 2>(ck);
-                        if (n > 2) bitonic_merge_ck<2, 4>(ck);
-                        if (n > 4) bitonic_merge_ck<4, 8>(ck);
-                        if (n > 8) bitonic_merge_ck<8, 16>(ck);
-                        if (n > 16) bitonic_merge_ck<16, 32>(ck);
-                        if (n > 32) bitonic_merge_ck<32, 0>(ck);
+                        static_assert(SCC_CODE_BITS <= 16, "the (group, code) sort key: 32 bits");
+                        u32 ck = kept ? (((u32)grp << SCC_CODE_BITS) | code) : ~0u;  // (grp <= 64)
+                        if (n > 1) bitonic_merge_ck32<1, 2>(ck);
+                        if (n > 2) bitonic_merge_ck32<2, 4>(ck);
+                        if (n > 4) bitonic_merge_ck32<4, 8>(ck);
+                        if (n > 8) bitonic_merge_ck32<8, 16>(ck);
+                        if (n > 16) bitonic_merge_ck32<16, 32>(ck);
+                        if (n > 32) bitonic_merge_ck32<32, 0>(ck);
                         n = nk;  // the kept elements, in (group, code) order in the first lanes
                         vl = lane < n;
-                        key = ck >> SCC_CODE_BITS;
-                        code = vl ? (u32)(ck & SCC_CODE_MASK) : 255u;
+                        key = (u64)(ck >> SCC_CODE_BITS);
+                        code = vl ? (ck & (u32)SCC_CODE_MASK) : 255u;
                     } else {
                         key = (u64)lane;  // every value its own group
                     }
@@ -2861,13 +2974,17 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                 for (int t = 0; t < NC; ++t)
 #pragma unroll
                     for (int d = 0; d < 4; ++d) ob[t][d] = (int)rk_eq_bytes((u32)cw[d], (u32)(r16 + 16 * t));
+                u32 hc[NC];  // (RUNS) the bucket's count of cluster r16 + 16 t, in every lane group
 #pragma unroll
                 for (int t = 0; t < NC; ++t) {  // the bucket's cluster histogram row
-                    u32 sm = (u32)ob[t][0] + (u32)ob[t][1] + (u32)ob[t][2] + (u32)ob[t][3];
-                    u32 c = (sm * 0x01010101u) >> 24;
-                    c += (u32)__shfl_xor((int)c, 16, 64);
-                    c += (u32)__shfl_xor((int)c, 32, 64);
-                    if (g4 == 0 && r16 + 16 * t < K) A.hbg[(size_t)bucket * K + r16 + 16 * t] = c;
+                    u32 c = 0;  // the sum of the sixteen 0 / 1 bytes
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) c = __builtin_amdgcn_sad_u8((u32)ob[t][d], 0u, c);
+                    c += rk_lane_at(at16, c);
+                    c += rk_lane_at(at32, c);
+                    hc[t] = c;
+                    if constexpr (!RUNS)
+                        if (g4 == 0 && r16 + 16 * t < K) A.hbg[(size_t)bucket * K + r16 + 16 * t] = c;
                 }
                 stamp(1);
                 // ---- M = L O (row tiles of 16 elements), R += O^T (2 M)
@@ -2893,11 +3010,48 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
                         const int t = rk_tile16<NC>(ma, nb);
                         R[t] = rk_mfma16(ob[ma], mb[nb], R[t]);
                     }
+                if constexpr (RUNS) {
+                    // ---- the run's cross term: rows 16 ma + 4 g4 + r of this bucket's
+                    // histogram against the prefix of column 16 nb + r16, then pre += h
+                    if (!wide) {
+#pragma unroll
+                        for (int ma = 0; ma < NC; ++ma) {
+                            u32 hr[4];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) hr[r] = rk_lane_at(atrow + 4 * r, 2u * hc[ma]);
+#pragma unroll
+                            for (int nb = ma; nb < NC; ++nb) {
+                                const int t = rk_tile16<NC>(ma, nb);
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) Cx[t][r] += (int)__umul24(hr[r], pre[nb]);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int t = 0; t < NC; ++t)
+                            if (g4 == 0) {
+                                Lw.cnt[r16 + 16 * t] = hc[t];
+                                Lw.pre[r16 + 16 * t] = pre[t];
+                            }
+                        wsync();
+                        const u32* tl = A.gene_tp + (size_t)g * P;
+                        for (int j = lane; j < ntp; j += 64) {
+                            const u32 v = tl[j];
+                            const u64 ca = Lw.cnt[(v >> 16) & 0xffu], pb = Lw.pre[v >> 24];
+                            if (ca && pb)
+                                atomicAdd((unsigned long long*)&A.accS[(size_t)(v & 0xffffu) * G + g],
+                                          (unsigned long long)(ca * pb));
+                        }
+                        wsync();
+                    }
+#pragma unroll
+                    for (int t = 0; t < NC; ++t) pre[t] += hc[t];
+                    npre += (u32)n;
+                }
                 stamp(2);
                 // ---- tie groups and runs
-                const u64 kp = ((u64)(u32)__shfl_up((int)(u32)(key >> 32), 1, 64) << 32) |
-                               (u64)(u32)__shfl_up((int)(u32)key, 1, 64);
-                const u32 cpv = (u32)__shfl_up((int)code, 1, 64);
+                const u64 kp = ((u64)rk_lane_up1((u32)(key >> 32)) << 32) | (u64)rk_lane_up1((u32)key);
+                const u32 cpv = rk_lane_up1(code);
                 const u64 vmask = (n >= 64) ? ~0ull : ((1ull << n) - 1);
                 const bool gs_me = (lane == 0) || (kp != key);
                 const u64 gst = __ballot(gs_me && vl);
@@ -2928,7 +3082,7 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt) {
                         if (mt >= nmt) break;
-                        const int gsr = __shfl(gs, 16 * mt + r16, 64), ger = __shfl(ge, 16 * mt + r16, 64);
+                        const int gsr = (int)rk_lane_at(atcol + 64 * mt, (u32)gs), ger = (int)rk_lane_at(atcol + 64 * mt, (u32)ge);
                         rk_v4i eq;
 #pragma unroll
                         for (int d = 0; d < 4; ++d)
@@ -2955,6 +3109,7 @@ __global__ void __launch_bounds__(256, NC >= 3 ? 2 : 1) k_rank_mfma16(ScRankLaun
             }
         }
     }
+    if constexpr (RUNS) end_run();
     if (cur >= 0) flush();
     stamp(4);
     if (stm && lane == 0)
@@ -3004,6 +3159,59 @@ __global__ void __launch_bounds__(256) k_rank_cross(ScRankLaunch A)
         }
         s = u64_wave_sum(s);
         if (lane == 0 && s) atomicAdd((unsigned long long*)&A.accS[(size_t)p * A.G + g], (unsigned long long)s);
+    }
+}
+
+// The same over run rows (k_rank_mfma16<NC, true, true>): within a run the
+// bucket kernel has added the term itself, so what is left is
+//   S_ab += sum over runs r of H_r[a] * #(b-elements in the gene's earlier runs)
+// H_r the run's totals, in the hbg row of the run's first list slot.  A gene
+// with buckets [bk0, bk0 + nb) has a run in every chunk it touches, chunk c at
+// row max(bk0, c CH), CH from rk_chunk as in the bucket kernel.  A gene has few
+// runs (config B: four of 16 buckets) and up to 120 tested pairs, so a wave
+// takes a gene, a lane a tested pair of its list, and walks the runs in order
+// with the b-count so far in a register, four rows' loads in flight together
+// (a wave per (gene, pair) with the lanes over runs was a chain of four
+// dependent loads per pair, 19 pairs a wave in turn: 54 us at B).  A gene of
+// one run owes nothing.
+__global__ void __launch_bounds__(256) k_rank_cross_runs(ScRankLaunch A)
+{
+    const int lane = threadIdx.x & 63;
+    const int W = blockIdx.x * 4 + scc_wave_id(), NW = gridDim.x * 4;
+    const int ng = split_count(A), P = A.P, K = A.K, nbig = A.counts[SCC_CNT_STRIDE * (13)];
+    const int CH = rk_chunk(min(A.counts[SCC_CNT_STRIDE * (4)], A.bucket_cap), A.rk_grid);
+    for (int gi = W; gi < ng; gi += NW) {
+        const int g = split_gene_at(A, nbig, gi);
+        const int bk0 = A.gene_bk[2 * g], nb = A.gene_bk[2 * g + 1];
+        if (nb < 1) continue;
+        const int ch0 = bk0 / CH, nr = (bk0 + nb - 1) / CH - ch0 + 1;
+        if (nr < 2) continue;
+        const int ntp = min(A.gene_nt[g], P);
+        const u32* tl = A.gene_tp + (size_t)g * P;
+        for (int j0 = 0; j0 < ntp; j0 += 64) {
+            const int j = j0 + lane;
+            const u32 v = tl[min(j, ntp - 1)];
+            const int a = (int)((v >> 16) & 0xffu), b = (int)(v >> 24);
+            u64 s = 0, below = 0;
+            for (int r0 = 0; r0 < nr; r0 += 4) {
+                u32 ha[4], hb[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {  // (rows past the gene's last run: the last run's again, zeroed)
+                    const int r = min(r0 + u, nr - 1);
+                    const unsigned int* h = A.hbg + (size_t)max(bk0, (ch0 + r) * CH) * K;
+                    ha[u] = h[a];
+                    hb[u] = h[b];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (r0 + u < nr) {
+                        s += (u64)ha[u] * below;
+                        below += hb[u];
+                    }
+                }
+            }
+            if (j < ntp && s) atomicAdd((unsigned long long*)&A.accS[(size_t)(v & 0xffffu) * A.G + g], (unsigned long long)s);
+        }
     }
 }
 
@@ -3277,7 +3485,9 @@ static hipError_t rank_waves_launches_t(const ScRankLaunch* L, int grid, SideStr
         M.wv_lo = mfma_min;
         st = place(4);
         M.wv_hi = 1 << 30;
-        if (L->K <= 16)
+        if (L->K <= 16 && VORD && L->rank_runs && !M.wv_filter)
+            hipLaunchKernelGGL((k_rank_mfma16<1, VORD, VORD>), dim3(grid), dim3(256), 0, st, M);
+        else if (L->K <= 16)
             hipLaunchKernelGGL((k_rank_mfma16<1, VORD>), dim3(grid), dim3(256), 0, st, M);
         else if (L->K <= 32)
             hipLaunchKernelGGL((k_rank_mfma16<2, VORD>), dim3(grid), dim3(256), 0, st, M);
@@ -3297,12 +3507,15 @@ static hipError_t rank_waves_launches_t(const ScRankLaunch* L, int grid, SideStr
         M.wv_filter = mfma ? 1 : 0;
         M.wv_lo = -1;
         M.wv_hi = mfma ? mfma_min : (1 << 30);
-        if (L->K <= 16)
+        if (L->K <= 16 && VORD && L->rank_runs && !M.wv_filter)
+            hipLaunchKernelGGL((k_rank_mfma16<1, VORD, VORD>), dim3(grid), dim3(256), 0, st, M);
+        else if (L->K <= 16)
             hipLaunchKernelGGL((k_rank_mfma16<1, VORD>), dim3(grid), dim3(256), 0, st, M);
         else
             hipLaunchKernelGGL((k_rank_mfma16<2, VORD>), dim3(grid), dim3(256), 0, st, M);
         return hipGetLastError();
     }
+    if (L->rank_runs) return hipErrorInvalidValue;  // (run rows come from the matrix-core kernel alone)
     for (int c = 0; c < 4; ++c) {
         if (c > 0 && 64 * L->rw_slots < hi[c]) break;
         if (mfma && hi[c] > mfma_min) return hipSuccess;  // the genes past mfma_min: done on the matrix cores
@@ -3416,7 +3629,9 @@ extern "C" hipError_t scc_launch_rank_cross(const ScRankLaunch* L, int grid, hip
 {
     // per-gene workgroups pay off once genes have many tested pairs (at P = 66 the
     // per-(gene, pair) waves are 12 us faster; at P >= 435 the gene kernel wins)
-    if (L->P > 128 && !L->cross_wave)
+    if (L->rank_runs)  // the bucket kernel left run rows (K <= 16: P <= 120)
+        hipLaunchKernelGGL(k_rank_cross_runs, dim3(grid), dim3(256), 0, st, *L);
+    else if (L->P > 128 && !L->cross_wave)
         hipLaunchKernelGGL(k_rank_cross_gene<false>, dim3(grid), dim3(XC_T), 0, st, *L);
     else  // one wave per (gene, pair) (SCC_CROSS_WAVE=1 selects it for comparisons)
         hipLaunchKernelGGL(k_rank_cross<false>, dim3(grid), dim3(256), 0, st, *L);

@@ -500,6 +500,10 @@ void scc_rt::vorder_free(const scc_dataset* d)
 // shards, the one-vs-rest run), 2 the walk of the dataset's value order
 thread_local int scc_rt::g_rank_last_route = 0;
 extern "C" SCC_API int scc_diag_rank_last_route(void) { return g_rank_last_route; }
+// 1: that run (route 2) formed the cross-bucket term per run, from one histogram
+// row per (gene, chunk); 0: a row per bucket and k_rank_cross, or no such run
+thread_local int scc_rt::g_rank_last_runs = 0;
+extern "C" SCC_API int scc_diag_rank_last_runs(void) { return g_rank_last_runs; }
 
 // which ingest the calling thread's last DE run took: 0 none yet, 1 the full
 // read (the validating call, SLOW, dense, SCC_INGEST_FULL), 2 the lean
