@@ -502,6 +502,31 @@ SCC_API int scc_cutree_hybrid_scores(scc_ctx* ctx, const int32_t* merge, const d
 SCC_API int scc_silhouette_scores(scc_ctx* ctx, int64_t n_cells, const int32_t* groups /* host [N] */,
                                   const void* scores /* device [n][16], NULL = kept */, double* widths,
                                   double* clus_avg, int32_t* n_groups);
+/* The exact k nearest neighbours of every cell under dist(scores), the search
+ * umap::umap(d = pca.data) and every other graph method on the scores starts with,
+ * without the packed vector or an n x n matrix.  For cell i: the k cells j != i with the
+ * smallest d(i, j), ordered by (distance ascending, index ascending); the same key decides
+ * which cell holds the k-th place, so the result does not depend on how the columns are
+ * tiled, chunked or merged, and two calls return the same bits.  d(i, j) is computed from
+ * score rows i and j with the dist kernel's arithmetic: dist[i][.] are bit for bit entries of
+ * the f64 scc_distance_scores output of the same scores.  dims: only the first dims
+ * components enter and the others are taken as zero (the README's pca.obj$x[, 1:8]), bit
+ * for bit the dims = 0 call on a copy whose other components are zeroed; the caller makes
+ * no copy.  scores: as scc_hclust_ward_d2_scores (read only; NULL = the kept scores).
+ * Device memory: the scores, 12 n k bytes of result, 12 k bytes per row of a launch and
+ * column chunk (at most 16 chunks) of partial lists, O(n) besides.  Launches are split by
+ * row blocks of about 2^36 entries (SCC_KNN_ROWS_PER_LAUNCH overrides the rows).
+ *   SCC_ERR_INVALID      no kept scores or scores of another size, k < 1 or k > n - 1,
+ *                        dims outside 0..15
+ *   SCC_ERR_UNSUPPORTED  k > SCC_KNN_MAX_K
+ *   SCC_ERR_NONFINITE    a non-finite score (counted on the device before any output is
+ *                        copied; no NaN distance is returned)
+ * A refused call leaves the context, the kept scores and any kept distance as they were.
+ * Runs on devices[0] only (timer family "knn_scores", one entry per call). */
+#define SCC_KNN_MAX_K 64
+SCC_API int scc_knn_scores(scc_ctx* ctx, int64_t n, const void* scores /* device [n][16], NULL = kept */,
+                           int32_t dims /* 1..15, 0 = all */, int32_t k,
+                           int32_t* idx /* host [n][k], 0-based */, double* dist /* host [n][k], may be NULL */);
 
 /* ---- heatmap inputs (cellTypeDEPlot.R:168-253) ---------------------------
  * What both reference functions end with (Fast:456-464, slow:288-296):

@@ -185,6 +185,42 @@ sccHeatmapRows <- function(dataset, deGeneUnion) {
   tree
 }
 
+# ---- the neighbour graph of the cells on the engine --------------------------
+# The reference README's example ends with prcomp_irlba(n = 15) on the marker
+# union, pca.data <- pca.obj$x[, 1:8] and umap::umap(d = pca.data), whose first
+# step is a k-nearest-neighbour search over the cells.  sccKnn runs the PCA and
+# that search on the engine (C_scc_knn: exact, no N x N matrix) and returns
+# list(indexes, distances), two N x k matrices, indexes 1-based, each row in
+# (distance, index) order: the shape umap::umap.knn(indexes, distances) takes
+# for umap(d, knn = ), and uwot's nn_method = list(idx = , dist = ).
+#   genes         row names or 1-based row indices (the marker union)
+#   n             components the PCA keeps (at most 15)
+#   dims          leading components the distance uses (the README's 8)
+#   include_self  TRUE: column 1 is the cell itself at distance 0, followed by
+#                 its k - 1 nearest other cells; FALSE: the k nearest others.
+#                 Whether a package expects the cell itself first was not
+#                 checked against umap or uwot (neither was at hand), which is
+#                 why it is a parameter: compare with the package's own
+#                 knn output before relying on the default.
+sccKnn <- function(dataMatrix, genes, k = 15, n = 15, dims = 8, include_self = TRUE) {
+  rows <- if (is.character(genes)) match(genes, rownames(dataMatrix)) else as.integer(genes)
+  if (anyNA(rows)) stop("sccKnn: a gene is not a row of the matrix")
+  others <- as.integer(k) - if (include_self) 1L else 0L
+  if (others < 1L) stop("sccKnn: k leaves no neighbour besides the cell itself")
+  if (dims < 1L || dims > n) stop("sccKnn: dims must lie in 1..n")
+  h <- .scc_dataset(dataMatrix)
+  on.exit(.Call("C_scc_release", h), add = TRUE)
+  t <- .Call("C_scc_knn", h, as.integer(rows), as.integer(n), as.integer(dims), others)
+  indexes <- t[[1]]
+  distances <- t[[2]]
+  if (include_self) {
+    indexes <- cbind(seq_len(nrow(indexes)), indexes)
+    distances <- cbind(0, distances)
+  }
+  rownames(indexes) <- rownames(distances) <- colnames(dataMatrix)
+  list(indexes = indexes, distances = distances)
+}
+
 # The drawing for options(scConsensus.engineHeatmapRows = TRUE): the wrapper's
 # own plotting helper, written from ComplexHeatmap's documented arguments.  Rows
 # follow the engine's tree (cluster_rows = a dendrogram, row_dend_reorder =

@@ -34,6 +34,8 @@
  *                   and the cuts are computed from them, no distance exists
  *   C_scc_si_scores C_scc_si on that route, from the engine-kept scores
  *                   (options(scConsensus.engineScoresSI = TRUE))
+ *   C_scc_knn       sccKnn: the exact k nearest neighbours of every cell from the
+ *                   PCA scores, the search umap(d = pca.data) starts with
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -489,6 +491,41 @@ SEXP C_scc_pca_scores(SEXP h, SEXP genes, SEXP ncomp)
     return Rf_ScalarInteger(N);
 }
 
+/* sccKnn: the PCA of C_scc_pca_scores (prcomp_irlba(n = ncomp) of the reference
+ * README's example), then the exact k nearest other cells of every cell under
+ * dist(scores[, 1:dims]) (scc_knn_scores: no N x N matrix).  Returns
+ * list(indexes, distances), N x k matrices, indexes 1-based, each row ordered
+ * by (distance, index); the cell itself is not listed (the R wrapper adds it). */
+SEXP C_scc_knn(SEXP h, SEXP genes, SEXP ncomp, SEXP dims, SEXP k)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes), kk = Rf_asInteger(k);
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int q = 0; q < nu; ++q) {
+        g0[q] = INTEGER(genes)[q] - 1;
+        if (g0[q] < 0 || g0[q] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[q] + 1);
+    }
+    if (kk < 1 || kk > N - 1) Rf_error("scConsensus engine: k = %d neighbours of %d cells", kk, N);
+    check(scc_pca_scores(g_ctx, ds, g0, nu, Rf_asInteger(ncomp)));
+    int32_t* idx = (int32_t*)R_alloc((size_t)N * kk, sizeof(int32_t)); /* row-major [N][k] */
+    double* dist = (double*)R_alloc((size_t)N * kk, sizeof(double));
+    check(scc_knn_scores(g_ctx, N, NULL, Rf_asInteger(dims), kk, idx, dist));
+    SEXP ri = PROTECT(Rf_allocMatrix(INTSXP, N, kk));
+    SEXP rd = PROTECT(Rf_allocMatrix(REALSXP, N, kk));
+    for (int i = 0; i < N; ++i)
+        for (int s = 0; s < kk; ++s) { /* R matrices are column-major */
+            INTEGER(ri)[(size_t)s * N + i] = idx[(size_t)i * kk + s] + 1;
+            REAL(rd)[(size_t)s * N + i] = dist[(size_t)i * kk + s];
+        }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, ri);
+    SET_VECTOR_ELT(out, 1, rd);
+    UNPROTECT(3);
+    return out;
+}
+
 /* hclust(dist(scores), "ward.D2") from the engine-kept scores of n cells
  * (scc_hclust_ward_d2_scores: no N x N matrix anywhere) */
 SEXP C_scc_hclust_scores(SEXP n_cells)
@@ -593,6 +630,7 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_hclust_scores", (DL_FUNC)&C_scc_hclust_scores, 1},
     {"C_scc_cutree_scores", (DL_FUNC)&C_scc_cutree_scores, 4},
     {"C_scc_si_scores", (DL_FUNC)&C_scc_si_scores, 1},
+    {"C_scc_knn", (DL_FUNC)&C_scc_knn, 5},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

@@ -51,6 +51,7 @@ EXPORTS = [
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
     "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
+    "scc_knn_scores",
     "scc_gene_distance", "scc_hclust_complete", "scc_dendro_reorder", "scc_heatmap_raster",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_rank_last_route", "scc_diag_rank_last_runs", "scc_diag_mirror_last_uses", "scc_diag_hclust_last_scans",
@@ -160,6 +161,7 @@ def load():
         "scc_hclust_ward_d2_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp]),
         "scc_cutree_hybrid_scores": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
         "scc_silhouette_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(i32)]),
+        "scc_knn_scores": (ctypes.c_int, [vp, i64, vp, i32, i32, vp, vp]),
         "scc_gene_distance": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, vp]),
         "scc_hclust_complete": (ctypes.c_int, [vp, i64, vp, vp, vp]),
         "scc_dendro_reorder": (ctypes.c_int, [vp, i64, vp, vp, vp]),
@@ -700,6 +702,20 @@ class Engine:
                                                    ctypes.c_void_p(scores_device_ptr or None), _ptr(w), _ptr(ca),
                                                    ctypes.byref(k)))
         return w, ca[:k.value]
+
+    def knn_scores(self, N, k, dims=0, scores_device_ptr=None):
+        """The exact k nearest neighbours of every cell under dist(scores) of a
+        device [N][16] score matrix (same rule as hclust_ward_d2_scores),
+        without the N x N matrix: (idx int32 [N, k] 0-based, dist float64
+        [N, k]), each row ordered by (distance, index), the cell itself left
+        out; the distances are bit for bit entries of distance_scores.  Only
+        the first `dims` components enter (0: all 15)."""
+        N, k = int(N), int(k)
+        idx = np.empty((N, max(k, 1)), np.int32)
+        dist = np.empty((N, max(k, 1)))
+        self._check(self.lib.scc_knn_scores(self.ctx, N, ctypes.c_void_p(scores_device_ptr or None), int(dims), k,
+                                            _ptr(idx), _ptr(dist)))
+        return idx, dist
 
     # -------------------------------------------------------------- heatmap inputs
     def gene_distance(self, ds: Dataset, genes):

@@ -432,3 +432,54 @@ def findAllMarkers(dataMatrix, clusterLabels, minClusterSize=10, minPerCent=20, 
                          "avg_logFC": r.avg_logfc[s].copy(), "pct.1": r.pct1[s].copy(), "pct.2": r.pct2[s].copy(),
                          "p_val_adj": r.q[s].copy(), "kept": r.de[s].copy(), "top": r.top[s].copy()}
     return {"markers": markers, "union": list(gnames[res.union]), "union_idx": res.union, "clusters": names}
+
+
+def nearest_neighbors(dataMatrix, genes, k=15, ncomp=15, dims=None, include_self=True, device=0, *,
+                      gene_names=None):
+    """The exact k-nearest-neighbour graph of the cells from their PCA scores,
+    the search the reference README's last step starts with
+    (``prcomp_irlba(n = 15)`` on the marker union, ``pca.data <-
+    pca.obj$x[, 1:8]``, ``umap::umap(d = pca.data)``, README.md:152-155), on
+    the engine and without an N x N matrix (scc_pca_scores, scc_knn_scores).
+
+    genes: the gene rows the PCA runs on (findAllMarkers' ``union_idx``), as
+    0-based row indices, or as names when ``gene_names`` lists every row's
+    name.  ncomp: components the PCA keeps (at most 15).  dims: leading
+    components the distance uses (None: all ncomp; the README uses 8 of 15).
+
+    Returns ``{"indexes": int32 [N, k] 0-based, "distances": float64 [N, k],
+    "scores": float64 [N, ncomp]}``, each row ordered by (distance, index).
+    With ``include_self`` column 0 is the cell itself at distance 0 and the
+    k - 1 nearest other cells follow; without it, the k nearest other cells.
+    Whether a consumer expects the cell itself first differs between packages,
+    which is why it is a parameter."""
+    g = np.asarray(genes)
+    if g.dtype.kind in "USO":
+        if gene_names is None:
+            raise ValueError("genes given by name need gene_names")
+        pos = {name: r for r, name in enumerate(gene_names)}
+        try:
+            g = np.array([pos[name] for name in g], np.int32)
+        except KeyError as e:
+            raise ValueError(f"unknown gene {e.args[0]!r}") from None
+    g = np.ascontiguousarray(g, np.int32)
+    k, ncomp = int(k), int(ncomp)
+    dims = ncomp if dims is None else int(dims)
+    if not 1 <= dims <= ncomp:
+        raise ValueError("dims must lie in 1..ncomp")
+    others = k - 1 if include_self else k
+    if others < 1:
+        raise ValueError("k leaves no neighbour besides the cell itself")
+    eng = _engine(device)
+    ds = _upload(eng, _as_matrix(dataMatrix))
+    try:
+        N = ds.N
+        eng.pca_scores(ds, g, ncomp)
+        idx, dist = eng.knn_scores(N, others, dims)
+        scores = eng.last_pca_scores(N)
+    finally:
+        ds.close()
+    if include_self:
+        idx = np.concatenate([np.arange(N, dtype=np.int32)[:, None], idx], axis=1)
+        dist = np.concatenate([np.zeros((N, 1)), dist], axis=1)
+    return {"indexes": idx, "distances": dist, "scores": scores}

@@ -40,3 +40,34 @@ __device__ inline double scc_dist_entry15(const double* pi, double ni, const dou
     }
     return scc_sqrt_nr(s);
 }
+
+// The same two over the leading D components only, for rows whose other
+// components are zero (scc_knn.hip's `dims`): fma(0, 0, s) is s exactly and
+// 0 - 0 is 0, so the steps left out change no bit of the norm or the entry.
+template <int D>
+__device__ inline double scc_dist_norm_lead(const double* p)
+{
+    double n = 0.0;
+#pragma unroll
+    for (int q = 0; q < D; ++q) n = fma(p[q], p[q], n);
+    return n;
+}
+
+template <int D>
+__device__ inline double scc_dist_entry_lead(const double* pi, double ni, const double* pj, double nj)
+{
+    double dot = 0.0;
+#pragma unroll
+    for (int q = 0; q < D; ++q) dot = fma(pi[q], pj[q], dot);
+    const double nsum = ni + nj;
+    double s = fma(-2.0, dot, nsum);
+    if (s < 0x1p-20 * nsum) {
+        s = 0.0;
+#pragma unroll
+        for (int q = 0; q < D; ++q) {
+            const double dv = pi[q] - pj[q];
+            s = fma(dv, dv, s);
+        }
+    }
+    return scc_sqrt_nr(s);
+}

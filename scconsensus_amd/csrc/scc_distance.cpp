@@ -39,6 +39,10 @@ hipError_t scc_launch_silhouette(const void* D, int f32, int N, const int* lab, 
                                  double* width, hipStream_t st);
 hipError_t scc_launch_silhouette_scores(const double* P, int N, const int* lab, const int* cnt, int C, double* part,
                                         double* width, unsigned int* nonfinite, hipStream_t st);
+hipError_t scc_launch_scores_nonfinite(const double* P, int N, unsigned int* nonfinite, hipStream_t st);
+size_t scc_knn_scratch_entries(int N, int k, int rows_forced);
+hipError_t scc_launch_knn_scores(const double* P, int N, int dims, int k, int rows_forced, double* part_d, int* part_i,
+                                 int* idx, double* dist, hipStream_t st);
 hipError_t scc_launch_dist_euclid(const double* P, int N, int c_lo, int c_hi, void* out, int f32, hipStream_t st);
 hipError_t scc_launch_zscore(const double* Xc, int N, int nu, int ld, float* Z, int ldz, hipStream_t st);
 hipError_t scc_launch_pearson(const double* Xc, int N, int nu, int ld, float* Z, int ldz, int c_lo, int c_hi,
@@ -1235,6 +1239,46 @@ extern "C" int scc_silhouette_scores(scc_ctx* c, int64_t n_cells, const int32_t*
     int rc;
     if (!P && (rc = kept_scores(c, N, "scc_silhouette_scores", &P))) return rc;
     return silhouette_run(c, N, groups, nullptr, 0, P, false, widths, clus_avg, n_groups);
+}
+
+extern "C" int scc_knn_scores(scc_ctx* c, int64_t n, const void* scores, int32_t dims, int32_t k, int32_t* idx,
+                              double* dist)
+{
+    if (!c || !idx) return fail(c, SCC_ERR_INVALID, "scc_knn_scores: null argument");
+    if (n < 2 || n > ((int64_t)1 << 27)) return fail(c, SCC_ERR_INVALID, "scc_knn_scores: bad cell count");
+    if (dims < 0 || dims > 15) return fail(c, SCC_ERR_INVALID, "scc_knn_scores: dims outside 0..15");
+    if (k < 1 || k > n - 1) return fail(c, SCC_ERR_INVALID, "scc_knn_scores: k outside 1..n-1");
+    if (k > SCC_KNN_MAX_K) return fail(c, SCC_ERR_UNSUPPORTED, "scc_knn_scores: k above SCC_KNN_MAX_K");
+    const int N = (int)n;
+    scc_enter(c);
+    hipStream_t s0 = c->s0;
+    const double* P = (const double*)scores;
+    int rc;
+    if (!P && (rc = kept_scores(c, N, "scc_knn_scores", &P))) return rc;
+    const int rows_forced = env_int("SCC_KNN_ROWS_PER_LAUNCH", 0);
+    const size_t np = scc_knn_scratch_entries(N, k, rows_forced), nk = (size_t)N * k;
+    double *d_pd, *d_dist;
+    int *d_pi, *d_idx;
+    unsigned int* d_bad;
+    if ((rc = ws(c, "knn_part_d", np, &d_pd))) return rc;
+    if ((rc = ws(c, "knn_part_i", np, &d_pi))) return rc;
+    if ((rc = ws(c, "knn_dist", nk, &d_dist))) return rc;
+    if ((rc = ws(c, "knn_idx", nk, &d_idx))) return rc;
+    if ((rc = ws(c, "knn_bad", 1, &d_bad))) return rc;
+    {
+        Scope sc(c, "knn_scores", s0);
+        HIPCHK(c, scc_launch_scores_nonfinite(P, N, d_bad, s0));
+        HIPCHK(c, scc_launch_knn_scores(P, N, dims ? dims : 15, k, rows_forced, d_pd, d_pi, d_idx, d_dist, s0));
+    }
+    unsigned int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    // the count, read before any neighbour is copied, says whether they are an answer
+    if (bad) return fail(c, SCC_ERR_NONFINITE, "scc_knn_scores: the scores hold a non-finite entry");
+    HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, s0));
+    if (dist) HIPCHK(c, hipMemcpyAsync(dist, d_dist, sizeof(double) * nk, hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    return SCC_OK;
 }
 
 extern "C" int scc_last_pca_scores(const scc_ctx* c, double* scores, int32_t* ncomp)

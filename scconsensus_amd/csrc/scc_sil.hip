@@ -209,15 +209,22 @@ extern "C" hipError_t scc_launch_silhouette(const void* D, int f32, int N, const
     return hipGetLastError();
 }
 
+// *nonfinite = how many of the [N][16] scores P are not finite (also scc_knn_scores' check)
+extern "C" hipError_t scc_launch_scores_nonfinite(const double* P, int N, unsigned int* nonfinite, hipStream_t st)
+{
+    const size_t n = (size_t)N * 16;
+    hipLaunchKernelGGL(k_sil_clear, dim3(1), dim3(1), 0, st, nonfinite);
+    hipLaunchKernelGGL(k_sil_nonfinite, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, n, nonfinite);
+    return hipGetLastError();
+}
+
 // the widths of dist(P) for the [N][16] scores P; *nonfinite counts the scores
 // that are not finite (the caller refuses the widths then)
 extern "C" hipError_t scc_launch_silhouette_scores(const double* P, int N, const int* lab, const int* cnt, int C,
                                                    double* part, double* width, unsigned int* nonfinite,
                                                    hipStream_t st)
 {
-    const size_t n = (size_t)N * 16;
-    hipLaunchKernelGGL(k_sil_clear, dim3(1), dim3(1), 0, st, nonfinite);
-    hipLaunchKernelGGL(k_sil_nonfinite, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, n, nonfinite);
+    scc_launch_scores_nonfinite(P, N, nonfinite, st);
     const dim3 grid((N + 63) / 64, SIL_JCH, (C + 16 * SIL_CT - 1) / (16 * SIL_CT));
     hipLaunchKernelGGL(k_sil_sums<SilScores>, grid, dim3(256), 0, st, P, N, lab, C, part);
     hipLaunchKernelGGL(k_sil_widths, dim3((N + 255) / 256), dim3(256), 0, st, part, N, C, lab, cnt, width);
