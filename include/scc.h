@@ -528,6 +528,105 @@ SCC_API int scc_knn_scores(scc_ctx* ctx, int64_t n, const void* scores /* device
                            int32_t dims /* 1..15, 0 = all */, int32_t k,
                            int32_t* idx /* host [n][k], 0-based */, double* dist /* host [n][k], may be NULL */);
 
+/* ---- UMAP of the cells (README.md:143-160: umap::umap(d = pca.data)) -------
+ * The last step of the README's example on the device: the fuzzy simplicial set
+ * of a k-NN table (umap-learn's smooth_knn_dist, compute_membership_strengths
+ * and fuzzy_simplicial_set), the stochastic-gradient layout of a symmetric
+ * weighted graph, and both behind scc_knn_scores in one call.  Everything is
+ * f64, no floating-point atomic is used, every random draw is a pure function
+ * of (seed, epoch, edge, draw): two calls return the same bits.  Agreement with
+ * the umap, uwot or umap-learn packages has not been measured (none was
+ * available); the rules are restated in NumPy in tests/umap_reference.py.
+ * All three run on devices[0] only, in workspace buffers of their own ("um_*";
+ * scc_umap_scores also in scc_knn_scores'): a refused call leaves the context,
+ * the kept scores and any kept distance as they were. */
+typedef struct {
+    double local_connectivity; /* 1.0 only (else SCC_ERR_UNSUPPORTED) */
+    double bandwidth;          /* 1.0 only (else SCC_ERR_UNSUPPORTED) */
+    double set_op_mix_ratio;   /* in [0, 1]; 1 = the fuzzy union, 0 = the intersection */
+    int32_t n_epochs;          /* >= 1 (the R package's default: 200) */
+    int32_t negative_sample_rate; /* 0..64 (default 5) */
+    double a, b;               /* the curve 1 / (1 + a d^(2b)); 0, 0 = SCC_UMAP_A, SCC_UMAP_B */
+    double gamma;              /* repulsion strength (default 1) */
+    double learning_rate;      /* initial alpha (default 1) */
+    uint64_t seed;
+    int32_t reserved[4];
+} scc_umap_params;
+/* find_ab_params(spread = 1, min_dist = 0.1): scipy.optimize.curve_fit of 1 / (1 + a x^(2b)) to
+ * umap-learn's target curve at 300 points of [0, 3] */
+#define SCC_UMAP_A 1.5769434602697652
+#define SCC_UMAP_B 0.8950608778515733
+
+/* The fuzzy simplicial set of a k-NN table in scc_knn_scores' output form (0-based, the cell
+ * itself left out, each row ascending in distance), n_neighbors = k + 1 (the cell counts as
+ * its own first neighbour).  Per row i over its k entries d_ij:
+ *   rho_i    the smallest strictly positive d_ij (0 if none)
+ *   sigma_i  bisection lo = 0, hi = inf, mid = 1, at most 64 steps, on
+ *            psum = sum_j (d_ij - rho_i > 0 ? exp(-(d_ij - rho_i) / mid) : 1) against
+ *            target = log2(k + 1): stop at |psum - target| < 1e-5; psum > target: hi = mid,
+ *            mid = (lo + hi) / 2; else lo = mid and mid *= 2 while hi is infinite, else
+ *            mid = (lo + hi) / 2.  Then sigma_i = max(mid, 1e-3 mean(row i)) if rho_i > 0, else
+ *            max(mid, 1e-3 mean(all distances)) (row sums in entry order, the global sum one
+ *            fixed-shape reduction of the row sums)
+ *   w_ij     (d_ij - rho_i <= 0 || sigma_i == 0) ? 1 : exp(-(d_ij - rho_i) / sigma_i)
+ * An entry whose index is its own row is dropped.  With a = w_ij, b = w_ji (a missing entry
+ * counts as 0) and mix = set_op_mix_ratio the edge value is mix (a + b - a b) + (1 - mix) a b,
+ * bit for bit the same on (i, j) and (j, i); the edge set is the union of the table and its
+ * transpose (mix > 0) or their intersection (mix == 0).  Output: host CSR, columns ascending
+ * within a row, rows of any length up to n - 1; cap: the entries cols and vals hold (2 n k
+ * always suffices); *nnz the entries written.  rho, sigma: host [n], weights: host [n][k] (the
+ * directed w_ij, a dropped entry's included); each may be NULL.
+ *   SCC_ERR_INVALID      n < 2, k < 1 or k > n - 1, an index outside 0..n-1 or listed twice in
+ *                        a row, a negative distance, a row not ascending in distance,
+ *                        set_op_mix_ratio outside [0, 1], cap below the entries needed
+ *   SCC_ERR_NONFINITE    a non-finite distance
+ *   SCC_ERR_UNSUPPORTED  k > SCC_KNN_MAX_K, local_connectivity or bandwidth other than 1
+ * Timer family "umap_graph", one entry per call. */
+SCC_API int scc_umap_graph(scc_ctx* ctx, int64_t n, int32_t k, const int32_t* idx /* host [n][k] */,
+                           const double* dist /* host [n][k] */, const scc_umap_params* prm,
+                           int64_t* indptr /* host [n + 1] */, int32_t* cols /* host [cap] */,
+                           double* vals /* host [cap] */, int64_t cap, int64_t* nnz, double* rho, double* sigma,
+                           double* weights);
+/* The layout of a symmetric weighted graph (host CSR as scc_umap_graph returns it) from
+ * init [n][2] to Y [n][2], n_epochs epochs of one launch each on double-buffered positions:
+ * vertex i owns row i, reads every position from the previous epoch's buffer and is the only
+ * writer of its new position and of its row's schedule, so an edge is seen from both ends, each
+ * on its own schedule.  With w_max the largest weight, an edge of weight w acts when w > 0 and
+ * w >= w_max / n_epochs: period p = w_max / w, next = p and next_neg = p / nsr initially
+ * (nsr = negative_sample_rate).  Epoch e = 1 .. n_epochs, alpha = learning_rate (1 - (e - 1) /
+ * n_epochs); an edge (i, j) at place `slot` of cols acts iff next <= e:
+ *   attraction   d2 = |y_i - y_j|^2, c = d2 > 0 ? -2 a b d2^(b-1) / (a d2^b + 1) : 0,
+ *                move clip(c (y_i - y_j), -4, 4) per coordinate
+ *   m = floor((e - next_neg) / (p / nsr)) draws (0 <= m <= 65535; nsr = 0: none), then
+ *                next_neg += m p / nsr, next += p; draw s picks
+ *                v = ((mix64(seed + C ctr) >> 32) n) >> 32, C = 0x9E3779B97F4A7C15,
+ *                ctr = ((e nnz + slot) << 16) + s (mod 2^64), mix64 splitmix64's output
+ *                function (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *                z *= 0x94D049BB133111EB, z ^= z >> 31); v == i is skipped, else
+ *                c = d2 > 0 ? 2 gamma b / ((0.001 + d2)(a d2^b + 1)) : 0 and the move is
+ *                clip(c (y_i - y_v), -4, 4), or +4 in both coordinates when d2 == 0
+ *   y_i += alpha (the sum of i's moves: 16 lanes take the row's slots l, l + 16, ..., each adds
+ *                in slot order, attraction before the slot's draws, then one xor butterfly)
+ *   SCC_ERR_INVALID    n < 1, indptr not ascending from 0, a column outside 0..n-1, a negative
+ *                      weight, n_epochs < 1, a negative a or b, negative_sample_rate outside 0..64
+ *   SCC_ERR_NONFINITE  a non-finite weight, init coordinate, gamma or learning_rate
+ * Timer family "umap_layout", one entry per call. */
+SCC_API int scc_umap_layout(scc_ctx* ctx, int64_t n, const int64_t* indptr /* host [n + 1] */,
+                            const int32_t* cols, const double* vals, const double* init /* host [n][2] */,
+                            const scc_umap_params* prm, double* Y /* host [n][2] */);
+/* scc_knn_scores (k = n_neighbors - 1, same scores, dims and refusals), scc_umap_graph and
+ * scc_umap_layout in one call without the table or the graph leaving the device: bit for bit
+ * what the three calls return one after the other.  n_neighbors in 2..SCC_KNN_MAX_K + 1 and at
+ * most n.  init: host [n][2], or NULL for the first two score columns scaled so that the
+ * largest absolute coordinate is 10 (umap-learn's PCA initialisation without its noise term).
+ * Only Y crosses to the host, and the graph when indptr, cols and vals are given (cap, nnz:
+ * as scc_umap_graph; all three NULL: no graph is copied).  Timer families "knn_scores",
+ * "umap_graph" and "umap_layout", one entry per call each. */
+SCC_API int scc_umap_scores(scc_ctx* ctx, int64_t n, const void* scores /* device [n][16], NULL = kept */,
+                            int32_t dims /* 1..15, 0 = all */, int32_t n_neighbors, const scc_umap_params* prm,
+                            const double* init, double* Y /* host [n][2] */, int64_t* indptr, int32_t* cols,
+                            double* vals, int64_t cap, int64_t* nnz);
+
 /* ---- heatmap inputs (cellTypeDEPlot.R:168-253) ---------------------------
  * What both reference functions end with (Fast:456-464, slow:288-296):
  * cellTypeDEPlot(dataMatrix[deGeneUnion, ], ...) hands the |U| x N block to

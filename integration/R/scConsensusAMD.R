@@ -221,6 +221,38 @@ sccKnn <- function(dataMatrix, genes, k = 15, n = 15, dims = 8, include_self = T
   list(indexes = indexes, distances = distances)
 }
 
+# ---- UMAP of the cells on the engine -----------------------------------------
+# The README's last step, umap::umap(d = pca.data), in one engine call
+# (C_scc_umap: the PCA, the exact neighbour search, the fuzzy simplicial set and
+# the stochastic-gradient layout; the table and the graph stay on the device).
+# Returns the N x 2 layout, rows named by cell: what umap::umap(...)$layout holds.
+# The rules are umap-learn's; the result is deterministic for a seed, and it has
+# not been compared with the umap or uwot packages (neither was at hand).
+#   n_neighbors   counts the cell itself, as umap.defaults$n_neighbors does (2..65)
+#   a, b          the curve constants; NULL: the pair fitted for min_dist = 0.1,
+#                 spread = 1 (another min_dist or spread: fit a and b with
+#                 umap-learn's find_ab_params recipe, e.g. by nls(), and pass them)
+#   init          an N x 2 matrix, or NULL for the first two components scaled to
+#                 a largest absolute coordinate of 10 (no spectral initialisation)
+sccUmap <- function(dataMatrix, genes, n_neighbors = 15, n = 15, dims = 8, n_epochs = 200, a = NULL, b = NULL,
+                    gamma = 1, negative_sample_rate = 5, learning_rate = 1, set_op_mix_ratio = 1, seed = 0,
+                    init = NULL) {
+  rows <- if (is.character(genes)) match(genes, rownames(dataMatrix)) else as.integer(genes)
+  if (anyNA(rows)) stop("sccUmap: a gene is not a row of the matrix")
+  if (n_neighbors < 2L) stop("sccUmap: n_neighbors leaves no neighbour besides the cell itself")
+  if (dims < 1L || dims > n) stop("sccUmap: dims must lie in 1..n")
+  if (is.null(a) != is.null(b)) stop("sccUmap: give both a and b, or neither")
+  if (!is.null(init) && !identical(dim(init), c(ncol(dataMatrix), 2L))) stop("sccUmap: init must be N x 2")
+  par <- c(n_epochs, if (is.null(a)) 0 else a, if (is.null(b)) 0 else b, gamma, negative_sample_rate,
+           learning_rate, set_op_mix_ratio, seed, 0)
+  h <- .scc_dataset(dataMatrix)
+  on.exit(.Call("C_scc_release", h), add = TRUE)
+  layout <- .Call("C_scc_umap", h, as.integer(rows), as.integer(n), as.integer(dims), as.integer(n_neighbors),
+                  as.numeric(par), if (is.null(init)) NULL else matrix(as.numeric(init), ncol = 2))
+  rownames(layout) <- colnames(dataMatrix)
+  layout
+}
+
 # The drawing for options(scConsensus.engineHeatmapRows = TRUE): the wrapper's
 # own plotting helper, written from ComplexHeatmap's documented arguments.  Rows
 # follow the engine's tree (cluster_rows = a dendrogram, row_dend_reorder =

@@ -36,6 +36,8 @@
  *                   (options(scConsensus.engineScoresSI = TRUE))
  *   C_scc_knn       sccKnn: the exact k nearest neighbours of every cell from the
  *                   PCA scores, the search umap(d = pca.data) starts with
+ *   C_scc_umap      sccUmap: that search, UMAP's fuzzy simplicial set and its
+ *                   layout from the PCA scores in one engine call
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -526,6 +528,60 @@ SEXP C_scc_knn(SEXP h, SEXP genes, SEXP ncomp, SEXP dims, SEXP k)
     return out;
 }
 
+/* sccUmap: the PCA of C_scc_pca_scores, then scc_umap_scores on the kept scores
+ * (the neighbour search, the fuzzy simplicial set and the layout without the
+ * table or the graph leaving the device).  par: numeric(9) = n_epochs, a, b,
+ * gamma, negative_sample_rate, learning_rate, set_op_mix_ratio, seed (below
+ * 2^53), unused; init: an N x 2 numeric matrix or NULL (the first two score
+ * columns scaled to a largest absolute coordinate of 10).  Returns the N x 2
+ * layout. */
+SEXP C_scc_umap(SEXP h, SEXP genes, SEXP ncomp, SEXP dims, SEXP n_neighbors, SEXP par, SEXP init)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes), nn = Rf_asInteger(n_neighbors);
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int q = 0; q < nu; ++q) {
+        g0[q] = INTEGER(genes)[q] - 1;
+        if (g0[q] < 0 || g0[q] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[q] + 1);
+    }
+    if (nn < 2 || nn > N) Rf_error("scConsensus engine: n_neighbors = %d of %d cells", nn, N);
+    if (LENGTH(par) < 8) Rf_error("scConsensus engine: C_scc_umap needs 8 parameters");
+    const double* pv = REAL(par);
+    scc_umap_params prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.local_connectivity = 1.0;
+    prm.bandwidth = 1.0;
+    prm.n_epochs = (int32_t)pv[0];
+    prm.a = pv[1];
+    prm.b = pv[2];
+    prm.gamma = pv[3];
+    prm.negative_sample_rate = (int32_t)pv[4];
+    prm.learning_rate = pv[5];
+    prm.set_op_mix_ratio = pv[6];
+    prm.seed = (uint64_t)pv[7];
+    double* y0 = NULL;
+    if (!Rf_isNull(init)) { /* column-major N x 2 -> [N][2] */
+        if (LENGTH(init) != 2 * N) Rf_error("scConsensus engine: init must be an N x 2 matrix");
+        y0 = (double*)R_alloc((size_t)N * 2, sizeof(double));
+        for (int i = 0; i < N; ++i) {
+            y0[2 * (size_t)i] = REAL(init)[i];
+            y0[2 * (size_t)i + 1] = REAL(init)[(size_t)N + i];
+        }
+    }
+    check(scc_pca_scores(g_ctx, ds, g0, nu, Rf_asInteger(ncomp)));
+    double* y = (double*)R_alloc((size_t)N * 2, sizeof(double));
+    check(scc_umap_scores(g_ctx, N, NULL, Rf_asInteger(dims), nn, &prm, y0, y, NULL, NULL, NULL, 0, NULL));
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, N, 2));
+    for (int i = 0; i < N; ++i) {
+        REAL(out)[i] = y[2 * (size_t)i];
+        REAL(out)[(size_t)N + i] = y[2 * (size_t)i + 1];
+    }
+    UNPROTECT(1);
+    return out;
+}
+
 /* hclust(dist(scores), "ward.D2") from the engine-kept scores of n cells
  * (scc_hclust_ward_d2_scores: no N x N matrix anywhere) */
 SEXP C_scc_hclust_scores(SEXP n_cells)
@@ -631,6 +687,7 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_cutree_scores", (DL_FUNC)&C_scc_cutree_scores, 4},
     {"C_scc_si_scores", (DL_FUNC)&C_scc_si_scores, 1},
     {"C_scc_knn", (DL_FUNC)&C_scc_knn, 5},
+    {"C_scc_umap", (DL_FUNC)&C_scc_umap, 7},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

@@ -51,7 +51,7 @@ EXPORTS = [
     "scc_distance_scores", "scc_silhouette", "scc_last_pca_scores",
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
     "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
-    "scc_knn_scores",
+    "scc_knn_scores", "scc_umap_graph", "scc_umap_layout", "scc_umap_scores",
     "scc_gene_distance", "scc_hclust_complete", "scc_dendro_reorder", "scc_heatmap_raster",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_rank_last_route", "scc_diag_rank_last_runs", "scc_diag_mirror_last_uses", "scc_diag_hclust_last_scans",
@@ -81,6 +81,26 @@ class MarkersParams(ctypes.Structure):
     _fields_ = [("top_n", ctypes.c_int32), ("only_pos", ctypes.c_int32), ("test", ctypes.c_int32),
                 ("test_all", ctypes.c_int32), ("q_val_thrs", ctypes.c_double), ("log_fc_thrs", ctypes.c_double),
                 ("min_per_cent", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
+
+
+class UmapParams(ctypes.Structure):
+    _fields_ = [("local_connectivity", ctypes.c_double), ("bandwidth", ctypes.c_double),
+                ("set_op_mix_ratio", ctypes.c_double), ("n_epochs", ctypes.c_int32),
+                ("negative_sample_rate", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("learning_rate", ctypes.c_double), ("seed", ctypes.c_uint64),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+# find_ab_params(spread = 1, min_dist = 0.1) (scc.h: SCC_UMAP_A, SCC_UMAP_B)
+UMAP_A = 1.5769434602697652
+UMAP_B = 0.8950608778515733
+
+
+def _umap_params(set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, n_epochs=200, a=0.0, b=0.0, gamma=1.0,
+                 negative_sample_rate=5, learning_rate=1.0, seed=0):
+    return UmapParams(float(local_connectivity), float(bandwidth), float(set_op_mix_ratio), int(n_epochs),
+                      int(negative_sample_rate), float(a), float(b), float(gamma), float(learning_rate),
+                      int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 _lib = None
@@ -162,6 +182,9 @@ def load():
         "scc_cutree_hybrid_scores": (ctypes.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, P(dbl)]),
         "scc_silhouette_scores": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(i32)]),
         "scc_knn_scores": (ctypes.c_int, [vp, i64, vp, i32, i32, vp, vp]),
+        "scc_umap_graph": (ctypes.c_int, [vp, i64, i32, vp, vp, P(UmapParams), vp, vp, vp, i64, P(i64), vp, vp, vp]),
+        "scc_umap_layout": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(UmapParams), vp]),
+        "scc_umap_scores": (ctypes.c_int, [vp, i64, vp, i32, i32, P(UmapParams), vp, vp, vp, vp, vp, i64, P(i64)]),
         "scc_gene_distance": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, vp]),
         "scc_hclust_complete": (ctypes.c_int, [vp, i64, vp, vp, vp]),
         "scc_dendro_reorder": (ctypes.c_int, [vp, i64, vp, vp, vp]),
@@ -716,6 +739,80 @@ class Engine:
         self._check(self.lib.scc_knn_scores(self.ctx, N, ctypes.c_void_p(scores_device_ptr or None), int(dims), k,
                                             _ptr(idx), _ptr(dist)))
         return idx, dist
+
+    # -------------------------------------------------------------- UMAP
+    def umap_graph(self, idx, dist, set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0,
+                   return_rho_sigma=False):
+        """The fuzzy simplicial set of a k-NN table in knn_scores' output form
+        (n_neighbors = k + 1: the cell counts as its own first neighbour):
+        the symmetric CSR (indptr int64 [N + 1], cols int32, vals float64),
+        columns ascending within a row; with return_rho_sigma also the rows'
+        rho and sigma and the directed weights [N, k]."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        dist = np.ascontiguousarray(dist, np.float64)
+        if idx.ndim != 2 or idx.shape != dist.shape:
+            raise ValueError("idx and dist must be [N, k] arrays of one shape")
+        N, k = idx.shape
+        cap = max(2 * N * k, 1)
+        indptr, cols, vals = np.zeros(N + 1, np.int64), np.empty(cap, np.int32), np.empty(cap)
+        rho, sigma, w = np.empty(max(N, 1)), np.empty(max(N, 1)), np.empty((max(N, 1), max(k, 1)))
+        nnz = ctypes.c_int64()
+        prm = _umap_params(set_op_mix_ratio, local_connectivity, bandwidth)
+        self._check(self.lib.scc_umap_graph(self.ctx, N, k, _ptr(idx), _ptr(dist), ctypes.byref(prm), _ptr(indptr),
+                                            _ptr(cols), _ptr(vals), cap, ctypes.byref(nnz), _ptr(rho), _ptr(sigma),
+                                            _ptr(w)))
+        g = (indptr, cols[:nnz.value].copy(), vals[:nnz.value].copy())
+        return g + (rho[:N], sigma[:N], w[:N, :k]) if return_rho_sigma else g
+
+    def umap_layout(self, indptr, cols, vals, init, n_epochs=200, a=0.0, b=0.0, gamma=1.0, negative_sample_rate=5,
+                    learning_rate=1.0, seed=0):
+        """The stochastic-gradient layout of a symmetric weighted CSR graph
+        from init [N, 2]: float64 [N, 2].  a = b = 0: the constants fitted for
+        min_dist = 0.1, spread = 1.  Two calls return the same bits."""
+        indptr = np.ascontiguousarray(indptr, np.int64)
+        cols = np.ascontiguousarray(cols, np.int32)
+        vals = np.ascontiguousarray(vals, np.float64)
+        init = np.ascontiguousarray(init, np.float64)
+        N = len(indptr) - 1
+        if N < 1 or init.shape != (N, 2) or cols.shape != vals.shape or cols.ndim != 1:
+            raise ValueError("umap_layout: indptr [N + 1], cols and vals of one length, init [N, 2]")
+        if len(cols) < indptr[-1]:
+            raise ValueError("umap_layout: cols and vals are shorter than indptr[-1]")
+        Y = np.empty((N, 2))
+        prm = _umap_params(1.0, 1.0, 1.0, n_epochs, a, b, gamma, negative_sample_rate, learning_rate, seed)
+        self._check(self.lib.scc_umap_layout(self.ctx, N, _ptr(indptr), _ptr(cols), _ptr(vals), _ptr(init),
+                                             ctypes.byref(prm), _ptr(Y)))
+        return Y
+
+    def umap_scores(self, N, n_neighbors=15, dims=0, scores_device_ptr=None, init=None, n_epochs=200, a=0.0, b=0.0,
+                    gamma=1.0, negative_sample_rate=5, learning_rate=1.0, seed=0, set_op_mix_ratio=1.0,
+                    local_connectivity=1.0, bandwidth=1.0, return_graph=False):
+        """knn_scores (k = n_neighbors - 1), umap_graph and umap_layout in one
+        call on a device [N][16] score matrix (same rule as knn_scores), the
+        table and the graph staying on the device: the layout float64 [N, 2],
+        bit for bit what the three calls give; with return_graph also the CSR
+        triple.  init None: the first two score columns scaled so that the
+        largest absolute coordinate is 10."""
+        N, nn = int(N), int(n_neighbors)
+        if init is not None:
+            init = np.ascontiguousarray(init, np.float64)
+            if init.shape != (N, 2):
+                raise ValueError("init must be [N, 2]")
+        Y = np.empty((max(N, 1), 2))
+        prm = _umap_params(set_op_mix_ratio, local_connectivity, bandwidth, n_epochs, a, b, gamma,
+                           negative_sample_rate, learning_rate, seed)
+        nnz = ctypes.c_int64()
+        indptr = cols = vals = None
+        cap = 0
+        if return_graph:
+            cap = max(2 * N * max(nn - 1, 0), 1)
+            indptr, cols, vals = np.zeros(max(N, 0) + 1, np.int64), np.empty(cap, np.int32), np.empty(cap)
+        self._check(self.lib.scc_umap_scores(self.ctx, N, ctypes.c_void_p(scores_device_ptr or None), int(dims), nn,
+                                             ctypes.byref(prm), _ptr(init), _ptr(Y), _ptr(indptr), _ptr(cols),
+                                             _ptr(vals), cap, ctypes.byref(nnz)))
+        if return_graph:
+            return Y, (indptr, cols[:nnz.value].copy(), vals[:nnz.value].copy())
+        return Y
 
     # -------------------------------------------------------------- heatmap inputs
     def gene_distance(self, ds: Dataset, genes):

@@ -483,3 +483,71 @@ def nearest_neighbors(dataMatrix, genes, k=15, ncomp=15, dims=None, include_self
         idx = np.concatenate([np.arange(N, dtype=np.int32)[:, None], idx], axis=1)
         dist = np.concatenate([np.zeros((N, 1)), dist], axis=1)
     return {"indexes": idx, "distances": dist, "scores": scores}
+
+
+def umap_ab_params(min_dist=0.1, spread=1.0):
+    """The curve constants (a, b) of 1 / (1 + a d^(2b)) for min_dist and spread:
+    umap-learn's find_ab_params recipe (scipy.optimize.curve_fit on 300 points
+    of [0, 3 spread]).  Without scipy only the default pair is available, from
+    the constants that recipe gave (nat.UMAP_A, nat.UMAP_B)."""
+    min_dist, spread = float(min_dist), float(spread)
+    if not (spread > 0.0 and 0.0 <= min_dist <= spread):
+        raise ValueError("min_dist must lie in [0, spread] and spread be positive")
+    try:
+        from scipy.optimize import curve_fit
+    except ImportError:
+        if (min_dist, spread) == (0.1, 1.0):
+            return nat.UMAP_A, nat.UMAP_B
+        raise ValueError("fitting a, b for a non-default min_dist or spread needs scipy") from None
+    xv = np.linspace(0, spread * 3, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    (a, b), _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2 * b)), xv, yv)
+    return float(a), float(b)
+
+
+def umap(dataMatrix, genes, n_neighbors=15, ncomp=15, dims=None, n_epochs=200, min_dist=0.1, spread=1.0, seed=0,
+         init=None, set_op_mix_ratio=1.0, gamma=1.0, negative_sample_rate=5, learning_rate=1.0, return_graph=False,
+         device=0, *, gene_names=None):
+    """The reference README's last step, ``umap::umap(d = pca.data)`` on
+    ``pca.data <- pca.obj$x[, 1:8]`` (README.md:152-160), on the engine: the PCA
+    of the gene rows, the exact neighbour search, the fuzzy simplicial set and
+    the stochastic-gradient layout (scc_pca_scores, scc_umap_scores) without
+    the table or the graph leaving the device.  Deterministic for a seed.  The
+    rules are umap-learn's (tests/umap_reference.py restates them); agreement
+    with the umap, uwot or umap-learn packages has not been measured.
+
+    genes, ncomp, dims, gene_names: as ``nearest_neighbors``.  n_neighbors
+    counts the cell itself (2..65).  init: an [N, 2] array, or None for the
+    first two score columns scaled so that the largest absolute coordinate is
+    10 (no spectral initialisation).  a, b are fitted from min_dist and spread
+    (``umap_ab_params``).
+
+    Returns ``{"layout": float64 [N, 2], "graph": (indptr, cols, vals) or
+    None}``, the graph (symmetric CSR, columns ascending) only with
+    ``return_graph``."""
+    g = np.asarray(genes)
+    if g.dtype.kind in "USO":
+        if gene_names is None:
+            raise ValueError("genes given by name need gene_names")
+        pos = {name: r for r, name in enumerate(gene_names)}
+        try:
+            g = np.array([pos[name] for name in g], np.int32)
+        except KeyError as e:
+            raise ValueError(f"unknown gene {e.args[0]!r}") from None
+    g = np.ascontiguousarray(g, np.int32)
+    n_neighbors, ncomp = int(n_neighbors), int(ncomp)
+    dims = ncomp if dims is None else int(dims)
+    if not 1 <= dims <= ncomp:
+        raise ValueError("dims must lie in 1..ncomp")
+    if n_neighbors < 2:
+        raise ValueError("n_neighbors leaves no neighbour besides the cell itself")
+    a, b = umap_ab_params(min_dist, spread)
+    eng = _engine(device)
+    ds = _upload(eng, _as_matrix(dataMatrix))
+    try:
+        eng.pca_scores(ds, g, ncomp)
+        out = eng.umap_scores(ds.N, n_neighbors, dims, None, init, n_epochs, a, b, gamma, negative_sample_rate,
+                              learning_rate, seed, set_op_mix_ratio, return_graph=bool(return_graph))
+    finally:
+        ds.close()
+    return {"layout": out[0], "graph": out[1]} if return_graph else {"layout": out, "graph": None}

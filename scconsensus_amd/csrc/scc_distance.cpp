@@ -1255,6 +1255,28 @@ extern "C" int scc_knn_scores(scc_ctx* c, int64_t n, const void* scores, int32_t
     const double* P = (const double*)scores;
     int rc;
     if (!P && (rc = kept_scores(c, N, "scc_knn_scores", &P))) return rc;
+    int* d_idx;
+    double* d_dist;
+    if ((rc = knn_scores_device(c, N, P, dims, k, "scc_knn_scores", &d_idx, &d_dist))) return rc;
+    const size_t nk = (size_t)N * k;
+    HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, s0));
+    if (dist) HIPCHK(c, hipMemcpyAsync(dist, d_dist, sizeof(double) * nk, hipMemcpyDeviceToHost, s0));
+    HIPCHK(c, hipStreamSynchronize(s0));
+    return SCC_OK;
+}
+
+namespace scc_rt {
+
+int kept_scores_device(scc_ctx* c, int64_t N, const char* who, const double** P) { return kept_scores(c, N, who, P); }
+
+// scc_knn_scores' device stage (also the first stage of scc_umap_scores): the
+// k nearest others of every row of P in the workspace, [N][k] each, once the
+// count of non-finite scores has been read.  Arguments are checked by the caller.
+int knn_scores_device(scc_ctx* c, int N, const double* P, int dims, int k, const char* who, int** idx_out,
+                      double** dist_out)
+{
+    hipStream_t s0 = c->s0;
+    int rc;
     const int rows_forced = env_int("SCC_KNN_ROWS_PER_LAUNCH", 0);
     const size_t np = scc_knn_scratch_entries(N, k, rows_forced), nk = (size_t)N * k;
     double *d_pd, *d_dist;
@@ -1274,12 +1296,13 @@ extern "C" int scc_knn_scores(scc_ctx* c, int64_t n, const void* scores, int32_t
     HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s0));
     HIPCHK(c, hipStreamSynchronize(s0));
     // the count, read before any neighbour is copied, says whether they are an answer
-    if (bad) return fail(c, SCC_ERR_NONFINITE, "scc_knn_scores: the scores hold a non-finite entry");
-    HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, s0));
-    if (dist) HIPCHK(c, hipMemcpyAsync(dist, d_dist, sizeof(double) * nk, hipMemcpyDeviceToHost, s0));
-    HIPCHK(c, hipStreamSynchronize(s0));
+    if (bad) return fail(c, SCC_ERR_NONFINITE, std::string(who) + ": the scores hold a non-finite entry");
+    *idx_out = d_idx;
+    *dist_out = d_dist;
     return SCC_OK;
 }
+
+}  // namespace scc_rt
 
 extern "C" int scc_last_pca_scores(const scc_ctx* c, double* scores, int32_t* ncomp)
 {

@@ -316,6 +316,12 @@ extern thread_local int g_rank_last_runs;
 // the mirror (no regroup), bit 1 its last PCA gather read the mirror
 extern thread_local int g_mirror_last_uses;
 
+// scc_distance.cpp, for the stages that start from the scores (scc_umap.cpp):
+// what a NULL `scores` argument stands for, and scc_knn_scores' device stage
+// (idx and dist [N][k] in the workspace; the non-finite count already read)
+int kept_scores_device(scc_ctx* c, int64_t N, const char* who, const double** P);
+int knn_scores_device(scc_ctx* c, int N, const double* P, int dims, int k, const char* who, int** idx, double** dist);
+
 // after a synchronisation: the eigensolver flag an earlier device-output
 // scc_distance (which returns without synchronising) left in h_flag
 int check_pending_eig(scc_ctx* c);
