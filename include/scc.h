@@ -366,7 +366,11 @@ SCC_API int scc_distance_cols(scc_ctx* ctx, const scc_dataset* ds, const int32_t
  * The mean is the same double-double sum as the unsharded path's, combined in
  * rank order, so every rank sees identical bits; the eigensolve of the summed
  * Gram runs once (scc_pca_shard_eigen on rank 0, vectors broadcast) or on every
- * rank (scc_pca_shard_scores = eigen + project, single-rank use). */
+ * rank (scc_pca_shard_scores = eigen + project, single-rank use).
+ * Order: colsum, then gram, then eigen / project / scores; a call before its
+ * predecessor on the same context fails with SCC_ERR_INVALID.  An empty shard
+ * (cell_lo == cell_hi, a rank with no cells) is valid: SCC_OK with zero sums,
+ * a zero partial Gram and no score rows written. */
 SCC_API int scc_pca_shard_colsum(scc_ctx* ctx, const scc_dataset* ds, const int32_t* genes /* host */,
                                  int32_t n_union, int64_t cell_lo, int64_t cell_hi, void* part /* device */);
 SCC_API int scc_pca_shard_gram(scc_ctx* ctx, const void* parts /* device [world][2 n_union] */, int32_t world,

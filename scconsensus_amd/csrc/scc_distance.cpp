@@ -380,7 +380,8 @@ static int dist_impl(scc_ctx* c, const scc_dataset* ds, const int32_t* genes, in
     unsigned int* d_eig_err = nullptr;  // the hand-off's time-out flag, read back after the last launch
     if (metric == SCC_DIST_PCA_EUCLID) {
         double *d_slabs, *d_C, *d_W, *d_Z, *d_P, *d_escr;
-        const bool fused = scc_gram_tile_width(ld) == 64;  // centring folded into the 64-wide Gram and the scores
+        // centring folded into the 64-wide Gram and the scores (SCC_CENTER_FUSED=0, tests: the centring pass)
+        const bool fused = scc_gram_tile_width(ld) == 64 && env_int("SCC_CENTER_FUSED", 1) != 0;
         const int nchunk = gram_chunks(Npad);
         WS("d_slabs", (size_t)nchunk * ld * ld, d_slabs);
         WS("d_C", (size_t)ld * ld, d_C);

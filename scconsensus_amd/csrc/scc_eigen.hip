@@ -42,6 +42,11 @@
 #define FIN_T 1024
 #define FIN_W (FIN_T / 64)
 #define EIG_LDS_MAX (160 * 1024)
+// the dynamic LDS k_tridiag / k_tri_vectors may ask for: a workgroup's 160 KB
+// hold their static __shared__ variables too (a request of exactly 160 KB at
+// n = 1344, or 80 n bytes at 2040 <= n <= 2048, was an invalid dispatch)
+#define TRI_LDS_MAX (EIG_LDS_MAX - 64)
+#define VEC_LDS_MAX (EIG_LDS_MAX - 2048)
 #define EIG_MAX_WG 256
 #define EIG_SPIN_LIMIT (1u << 22)
 
@@ -983,10 +988,22 @@ __device__ __forceinline__ void tri_vector_item(const VecArgs& a, const int q)
         double* fp = fl + n;
         double* w = fp + n;  // forward-solve result
         const double tiny = kEps * tnorm + 1e-300;
+        // The solves use a shift 64 eps ||T|| above the bisected one.  Eigenvalues
+        // that agree to rounding (a rank-deficient Gram's null space, an exact
+        // multiple) get the same bisected shift, and at that shift the resolvent
+        // picks out the one or two eigenvectors that happen to lie nearest: the
+        // cluster's workgroups then return nearly the same vector, and k_eig_finish
+        // divides by what Gram-Schmidt leaves of it.  From 64 eps ||T|| away the
+        // unresolvable part of a cluster (spread ~eps ||T||) is amplified evenly,
+        // so each workgroup returns its own start vector's projection onto it.
+        // Everything separated by more than that is still resolved: a neighbour
+        // at distance g enters as (64 eps ||T|| / g)^2 after the two solves and
+        // adds at most ~64 eps ||T|| to the residual.
+        const double lams = lam + 64.0 * kEps * tnorm;
         if (tid == 0) {
             // inputs of LU_B steps are loaded together ahead of the dependent chain
             constexpr int LU_B = 8;
-            double dcur = dl[0] - lam, ucur = (n > 1) ? el[0] : 0.0;
+            double dcur = dl[0] - lams, ucur = (n > 1) ? el[0] : 0.0;
             for (int i0 = 0; i0 < n - 1; i0 += LU_B) {
                 double li[LU_B], dn[LU_B], un[LU_B];
     #pragma unroll
@@ -994,7 +1011,7 @@ __device__ __forceinline__ void tri_vector_item(const VecArgs& a, const int q)
                     const int i = i0 + u;
                     const double e0 = el[min(i, n - 1)], d1 = dl[min(i + 1, n - 1)], e1 = el[min(i + 1, n - 1)];
                     li[u] = e0;
-                    dn[u] = d1 - lam;
+                    dn[u] = d1 - lams;
                     un[u] = (i < n - 2) ? e1 : 0.0;
                 }
     #pragma unroll
@@ -1300,14 +1317,18 @@ __global__ void __launch_bounds__(FIN_T) k_eig_finish(double* Zq, int n, int lda
     const double tnorm = tnorm_p[0];
     for (int qq = 0; qq < k; ++qq) {  // vectors live in global memory (one workgroup)
         double* z = Zq + (size_t)qq * lda;
-        for (int rr = qq - 1; rr >= 0 && fabs(W[rr] - W[rr + 1]) <= 1e-3 * tnorm; --rr) {
-            const double* zr = Zq + (size_t)rr * lda;
-            double s = 0.0;
-            for (int i = tid; i < n; i += FIN_T) s += zr[i] * z[i];
-            s = block_sum<FIN_W>(s, red);
-            for (int i = tid; i < n; i += FIN_T) z[i] -= s * zr[i];
-            __syncthreads();
-        }
+        // two passes ("twice is enough"): where the cluster's vectors came out nearly
+        // parallel the first pass cancels most of z and leaves eps * |z before| / |z after|
+        // along its predecessors; the second pass removes that
+        for (int pass = 0; pass < 2; ++pass)
+            for (int rr = qq - 1; rr >= 0 && fabs(W[rr] - W[rr + 1]) <= 1e-3 * tnorm; --rr) {
+                const double* zr = Zq + (size_t)rr * lda;
+                double s = 0.0;
+                for (int i = tid; i < n; i += FIN_T) s += zr[i] * z[i];
+                s = block_sum<FIN_W>(s, red);
+                for (int i = tid; i < n; i += FIN_T) z[i] -= s * zr[i];
+                __syncthreads();
+            }
         double s = 0.0;
         for (int i = tid; i < n; i += FIN_T) s += z[i] * z[i];
         s = block_sum<FIN_W>(s, red);
@@ -1688,14 +1709,15 @@ __global__ void __launch_bounds__(FIN_T) k_eig_finish_lds(const double* Zq, int 
     for (int q = 1; q < k; ++q) {
         if (head(q)) continue;
         double* z = zl + (size_t)q * n;
-        for (int rr = q - 1; rr >= 0 && fabs(W[rr] - W[rr + 1]) <= 1e-3 * tnorm; --rr) {
-            const double* zr = zl + (size_t)rr * n;
-            double s = 0.0;
-            for (int i = tid; i < n; i += FIN_T) s += zr[i] * z[i];
-            s = block_sum<FIN_W>(s, red);
-            for (int i = tid; i < n; i += FIN_T) z[i] -= s * zr[i];
-            __syncthreads();
-        }
+        for (int pass = 0; pass < 2; ++pass)  // twice is enough (see k_eig_finish)
+            for (int rr = q - 1; rr >= 0 && fabs(W[rr] - W[rr + 1]) <= 1e-3 * tnorm; --rr) {
+                const double* zr = zl + (size_t)rr * n;
+                double s = 0.0;
+                for (int i = tid; i < n; i += FIN_T) s += zr[i] * z[i];
+                s = block_sum<FIN_W>(s, red);
+                for (int i = tid; i < n; i += FIN_T) z[i] -= s * zr[i];
+                __syncthreads();
+            }
         if (wv == 0) fin_wave_finalize(z, n, lane);
         __syncthreads();
     }
@@ -1793,7 +1815,7 @@ static bool eig_local(int n)
     if (env >= 0) return env != 0;
     int nwg = eig_nwg(n);
     if (nwg > 32) nwg = 32;
-    return tri_lds_bytes(n, std::max((n + nwg - 1) / nwg - tri_reg_rows(n), 0), true) <= EIG_LDS_MAX;
+    return tri_lds_bytes(n, std::max((n + nwg - 1) / nwg - tri_reg_rows(n), 0), true) <= TRI_LDS_MAX;
 }
 
 static void eig_plan(int n, int& nwg, bool& rows_lds, bool& lu_lds)
@@ -1801,8 +1823,8 @@ static void eig_plan(int n, int& nwg, bool& rows_lds, bool& lu_lds)
     nwg = eig_nwg(n);
     if (eig_local(n) && nwg > 32) nwg = 32;  // one XCD holds 32 CUs
     const int R = std::max((n + nwg - 1) / nwg - tri_reg_rows(n), 0);  // rows outside registers
-    rows_lds = tri_lds_bytes(n, R, true) <= EIG_LDS_MAX;
-    lu_lds = sizeof(double) * 10 * (size_t)n <= EIG_LDS_MAX;
+    rows_lds = tri_lds_bytes(n, R, true) <= TRI_LDS_MAX;
+    lu_lds = sizeof(double) * 10 * (size_t)n <= VEC_LDS_MAX;
 }
 
 // A non-blocking side stream (and fork / join events) per device for work
@@ -1972,7 +1994,7 @@ static hipError_t eig_direct(const double* A, int n, int lda, int k, double* scr
     hipError_t e;
     if (safe) {
         nwg = 1;
-        rows_lds = tri_lds_bytes(n, std::max(n - tri_reg_rows(n), 0), true) <= EIG_LDS_MAX;
+        rows_lds = tri_lds_bytes(n, std::max(n - tri_reg_rows(n), 0), true) <= TRI_LDS_MAX;
     }
     // granule tags restart at 1 every launch
     e = hipMemsetAsync(scratch + L.pg, 0, sizeof(double) * (L.zq - L.pg), st);
