@@ -867,7 +867,7 @@ static int rank_split_clocks(scc_ctx* c, hipStream_t s0, const int* d_counts)
 {
     int hc[SCC_NCOUNTS];
     HIPCHK(c, read_counts(d_counts, s0, hc));
-    scc_rank_split_diag(s0, hc[3] + hc[13]);  // (small split genes + large ones)
+    scc_rank_split_diag(s0, hc[RK_CNT_SPLIT_GENES] + hc[RK_CNT_BIG_GENES]);
     return SCC_OK;
 }
 
@@ -897,7 +897,9 @@ static int rank_log(scc_ctx* c, hipStream_t s0, const int* d_counts)
     int h[SCC_NCOUNTS];
     HIPCHK(c, read_counts(d_counts, s0, h));
     fprintf(stderr, "[scc rank] items %d/%d/%d split genes %d wave buckets %d bucket ids %d parents %d "
-            "segments %d second-level %d\n", h[0], h[1], h[2], h[3] + h[13], h[4], h[5], h[8], h[10], h[12]);
+            "segments %d second-level %d\n", h[RK_CNT_ITEMS0], h[RK_CNT_ITEMS0 + 1], h[RK_CNT_ITEMS0 + 2],
+            h[RK_CNT_SPLIT_GENES] + h[RK_CNT_BIG_GENES], h[RK_CNT_WAVE_SLOTS], h[RK_CNT_BUCKET_IDS], h[RK_CNT_FAT],
+            h[RK_CNT_SEGMENTS], h[RK_CNT_FAT2]);
     return SCC_OK;
 }
 
@@ -910,17 +912,17 @@ static int rank_stamps_report(scc_ctx* c, hipStream_t s0, const unsigned long lo
     HIPCHK(c, hipMemcpyAsync(h.data(), st_buf, h.size() * 8, hipMemcpyDeviceToHost, s0));
     HIPCHK(c, read_counts(d_counts, s0, cnts));
     const char* ph[] = {"setup", "sort", "fixup+codes", "partition", "pairs", "ties"};
-    fprintf(stderr, "[scc stamps] split genes %d\n", cnts[3]);
+    fprintf(stderr, "[scc stamps] split genes %d\n", cnts[RK_CNT_SPLIT_GENES]);
     for (int cls = 0; cls < 3; ++cls) {
         double acc[6] = {0, 0, 0, 0, 0, 0};
         int nb = 0;
-        for (int b = 0; b < cnts[cls]; ++b) {
+        for (int b = 0; b < cnts[RK_CNT_ITEMS0 + cls]; ++b) {
             const unsigned long long* t = &h[((size_t)cls * item_cap + b) * 8];
             if (!t[0] || !t[6]) continue;
             for (int q = 0; q < 6; ++q) acc[q] += (double)(t[q + 1] - t[q]);
             ++nb;
         }
-        fprintf(stderr, "[scc stamps] rank class %d: %d items (%d full), mean cycles:", cls, cnts[cls], nb);
+        fprintf(stderr, "[scc stamps] rank class %d: %d items (%d full), mean cycles:", cls, cnts[RK_CNT_ITEMS0 + cls], nb);
         for (int q = 0; q < 6; ++q) fprintf(stderr, " %s %.0f", ph[q], nb ? acc[q] / nb : 0.0);
         fprintf(stderr, "\n");
     }

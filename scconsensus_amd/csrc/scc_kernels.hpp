@@ -28,6 +28,24 @@ struct dd;
 #define SCC_NCOUNTS 16
 #define SCC_CNT_STRIDE 32
 
+// What each counter counts.  Kernels reach them through rk_cnt (scc_rank_dev.hpp),
+// the host through read_counts (scc_de.cpp); both index by these names.
+enum ScRankCounter {
+    RK_CNT_ITEMS0 = 0,          // items of class 0 (small, LDS), + 1: class 1 (medium, LDS), + 2: class 2 (HBM-resident)
+    RK_CNT_SPLIT_GENES = 3,     // ranked genes below SPLIT_BIG values: split_genes, filled from the front
+    RK_CNT_WAVE_SLOTS = 4,      // slots taken in the wave-bucket list (sbuckets)
+    RK_CNT_BUCKET_IDS = 5,      // global bucket ids handed out (rows of hbg)
+    RK_CNT_SPLIT_CURSOR = 6,    // the split's work-queue cursor over the ranked genes
+    RK_CNT_FAT = 8,             // re-split parents: entries taken in fatbk
+    RK_CNT_RESPLIT_CURSOR = 9,  // the workgroup re-split's work-queue cursor over (gene, slice)
+    RK_CNT_SEGMENTS = 10,       // re-split segments written to rsseg (in-parent cross terms)
+    RK_CNT_FAT_GENES = 11,      // genes with re-split parents: entries of fatg
+    RK_CNT_FAT2 = 12,           // second-level re-split parents pushed to fat2 (may pass fat2_cap)
+    RK_CNT_BIG_GENES = 13,      // ranked genes of >= SPLIT_BIG values: split_genes, filled from the far end
+    RK_CNT_END                  // one past the largest slot in use
+};
+static_assert(RK_CNT_END <= SCC_NCOUNTS, "a rank work counter past the counts array");
+
 struct ScStatsLaunch {
     const long long* gstart;
     const unsigned long long* keys;
@@ -75,9 +93,7 @@ struct ScRankLaunch {
     int* gene_bk;          // [2 G] first bucket id and bucket count of each split gene
     unsigned long long* gkmin;  // [G] key minimum of a split gene when its range fits 58 bits, else ~0
     ScRankItem* items;     // [3][item_cap]
-    int* counts;           // [0..2] items per class, [3] split genes, [4] wave buckets, [5] bucket ids,
-                           // [8] fat buckets, [9] re-split queue, [10] re-split segments, [11] re-split genes,
-                           // [12] second-level re-split parents
+    int* counts;           // the work counters, one per ScRankCounter name, SCC_CNT_STRIDE ints apart
     uint32_t* gene_tp;     // [G][P] tested pairs of each split gene, p | a << 16 | b << 24 (pair order)
     int* gene_nt;          // [G] their number
     int wv_lo, wv_hi;      // wave kernel launch: genes with wv_lo < tested pairs <= wv_hi
@@ -90,7 +106,7 @@ struct ScRankLaunch {
     int4* rsseg;           // [fat_cap] {gene, first sub-bucket id, sub-buckets}: in-parent cross terms
     int fat_cap;
     int rsw_chunk;         // wave re-split: bucket ids / list slots taken per global atomic
-    ScRankItem* fat2;      // [fat2_cap] second re-split level (counts[12])
+    ScRankItem* fat2;      // [fat2_cap] second re-split level (RK_CNT_FAT2 of them)
     int fat2_cap;
     int rs_level;          // wave re-split launch: 0 reads fatbk, 1 reads fat2
     int rsw_all;           // wave re-split: one launch takes every gene (no split by tested pairs)

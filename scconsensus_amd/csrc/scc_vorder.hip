@@ -14,8 +14,8 @@
 //                at most 64 entries and never divides a tie group; a tie group
 //                of more than 64 entries is a bucket of its own (bit 31)
 // The rank stage of a FAST Wilcoxon run over the whole gene range walks these
-// buckets and sorts only inside tie groups (scc_rank.hip: k_rank_vorder_list,
-// then the VORD variants of k_rank_mfma16 and k_rank_waves).
+// buckets and sorts only inside tie groups (scc_rank_split.hip: k_rank_vorder_list,
+// then the VORD variants of k_rank_mfma16 and k_rank_waves, scc_rank_waves.hip).
 //
 // The sort is rocPRIM's segmented radix sort of (key, cell) pairs, run over
 // blocks of whole genes so that its scratch fits what the caller lends it (two

@@ -1,5 +1,5 @@
 """Pure-numpy model of the GPU rank kernel's ALGORITHM (scconsensus_amd/csrc/
-scc_rank.hip), used only by tests to validate the count formula on the CPU
+scc_rank_*.hip), used only by tests to validate the count formula on the CPU
 against the oracle's R-style rank sums.  Not product code.
 
 Per gene: kept nonzeros sorted by (value, cluster code); S[a][b] = number of
@@ -77,7 +77,8 @@ def _okey(v):
 
 
 def gene_u2_ties_buckets(values, codes, n_clu, target=8, bins_bits=11):
-    """The kernel pipeline (scc_rank.hip): the nonzeros are cut into value
+    """The kernel pipeline (scc_rank_split.hip, scc_rank_item.hip,
+    scc_rank_cross.hip): the nonzeros are cut into value
     buckets (k_rank_split: 2^bins_bits-bin histogram of the key window, runs
     of bins with equal floor(excl / target), fat bins alone); the
     cross-bucket part of S comes from per-bucket cluster histograms; inside a

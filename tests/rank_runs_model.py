@@ -1,6 +1,6 @@
 """Numpy statement of the run rows of the rank stage (scconsensus_amd/csrc/
-scc_rank.hip: rk_chunk, k_rank_mfma16<1, true, true>, k_rank_cross_runs).  Test
-code only.
+scc_rank_dev.hpp: rk_chunk; scc_rank_waves.hip: k_rank_mfma16<1, true, true>;
+scc_rank_cross.hip: k_rank_cross_runs).  Test code only.
 
 A gene's buckets sit at consecutive slots [bk0, bk0 + nb) of the bucket list,
 in value order.  The bucket kernel takes the list in chunks of CH slots; a

@@ -1,5 +1,5 @@
 """CPU: the engine's count-based rank-sum algorithm (modelled in numpy by
-tests/engine_model.py, mirroring scc_rank.hip) equals R's rank definition
+tests/engine_model.py, mirroring scc_rank_*.hip) equals R's rank definition
 (the oracle) exactly, including zeros, negatives and cross-cluster ties."""
 import numpy as np
 import pytest

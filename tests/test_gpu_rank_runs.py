@@ -1,6 +1,6 @@
-"""The rank stage's run rows (scc_rank.hip: k_rank_mfma16<1, true, true> adds the
+"""The rank stage's run rows (scc_rank_waves.hip: k_rank_mfma16<1, true, true> adds the
 cross-bucket term inside each run of a gene's buckets and leaves one histogram
-row per run; k_rank_cross_runs sums over those rows) against the route it
+row per run; k_rank_cross_runs, scc_rank_cross.hip, sums over those rows) against the route it
 replaces at K <= 16 (a row per bucket, k_rank_cross over buckets;
 SCC_RANK_RUNS=0), bit for bit.  The reference ranks every pair's cells again
 (R/reclusterDEConsensusFast.R, the wilcox.test calls of the per-pair loop): one

@@ -1,5 +1,5 @@
-"""The rank stage on the dataset's value order (scc_vorder.hip; scc_rank.hip:
-k_rank_vorder_list, k_rank_mfma16<1, true>) against the per-call value buckets
+"""The rank stage on the dataset's value order (scc_vorder.hip; k_rank_vorder_list in
+scc_rank_split.hip, k_rank_mfma16<1, true> in scc_rank_waves.hip) against the per-call value buckets
 it replaces (split, re-split, in-wave sort, LDS items), bit for bit on the
 fields tests/test_gpu_mirror.py compares.  A dataset that keeps the gene-major
 mirror keeps each gene's ascending value order and its bucket cuts; a FAST

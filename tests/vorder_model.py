@@ -1,6 +1,7 @@
 """Numpy statement of the value order's bucket cuts (scconsensus_amd/csrc/
 scc_vorder.hip, k_vord_cuts) and of the sums the rank stage takes over them
-(scc_rank.hip, k_rank_mfma16<1, true> and k_rank_cross).  Test code only.
+(k_rank_mfma16<1, true> in scc_rank_waves.hip and k_rank_cross in
+scc_rank_cross.hip).  Test code only.
 
 A gene's stored values are in ascending order (equal values in cell order).
 From a bucket's start s the candidates for its end are the positions e in
