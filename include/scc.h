@@ -631,6 +631,89 @@ SCC_API int scc_umap_scores(scc_ctx* ctx, int64_t n, const void* scores /* devic
                             const double* init, double* Y /* host [n][2] */, int64_t* indptr, int32_t* cols,
                             double* vals, int64_t cap, int64_t* nnz);
 
+/* ---- SNN graph and modularity clustering of the cells ----------------------
+ * The step in front of the README's example: its `seuratObj$RNA_snn_res.0.2` is
+ * what Seurat's FindNeighbors + FindClusters make of the PCA scores.  Here: the
+ * shared-nearest-neighbour graph of a k-NN table by Seurat's ComputeSNN rule,
+ * a deterministic multilevel modularity clustering of a symmetric weighted
+ * graph, and both behind scc_knn_scores in one call.  No floating-point atomic
+ * is used; the clustering's weights are integers, so its sums are exact in any
+ * order: two calls return the same bits.  Agreement with Seurat, igraph or
+ * leidenalg has not been measured (none was available); the rules are restated
+ * in NumPy in tests/snn_reference.py.  Not done: Leiden or SLM refinement,
+ * Seurat's grouping of singletons, a random vertex order, more than one device.
+ * All three run on devices[0] only, in workspace buffers of their own ("sn_*",
+ * "mc_*"; the fused call also in scc_knn_scores'): a refused call leaves the
+ * context, the kept scores and any kept distance as they were. */
+
+/* The SNN graph of a k-NN table in scc_knn_scores' output form (0-based, the cell itself left
+ * out; distances are not an input).  K = k + 1 is Seurat's k.param, N_i = {i} + idx[i].  For
+ * every pair i != j with s = |N_i & N_j| >= 1 (every two-hop pair, not only listed
+ * neighbours): w = (double)s / (double)(K + (K - s)), kept iff w >= prune in f64.  The diagonal
+ * (Seurat stores w = 1 there) is NOT stored: a choice of this engine, so that the output feeds
+ * scc_modularity_cluster as it is.  Output: host CSR as scc_umap_graph returns it (indptr
+ * int64, columns ascending within a row, (i, j) and (j, i) the same bits), rows of any length up
+ * to n - 1; shared: the counts s parallel to vals, or NULL.  cap: the entries cols, vals and
+ * shared hold; *nnz the graph's entries.  No bound such as 2 n k holds: when cap is too small
+ * the call returns SCC_ERR_INVALID with *nnz set to the entries needed, and the caller may call
+ * again.
+ *   SCC_ERR_INVALID      n < 2, k < 1 or k > n - 1, an index outside 0..n-1 or listed twice in
+ *                        a row, a row listing itself, prune outside [0, 1], cap too small
+ *   SCC_ERR_NONFINITE    a non-finite prune
+ *   SCC_ERR_UNSUPPORTED  k > SCC_KNN_MAX_K
+ * Timer family "snn_graph", one entry per call. */
+SCC_API int scc_snn_graph(scc_ctx* ctx, int64_t n, int32_t k, const int32_t* idx /* host [n][k] */,
+                          double prune /* Seurat's default: 1.0 / 15 */, int64_t* indptr /* host [n + 1] */,
+                          int32_t* cols /* host [cap] */, double* vals /* host [cap] */,
+                          int32_t* shared /* host [cap] or NULL */, int64_t cap, int64_t* nnz);
+/* Multilevel modularity clustering of a symmetric weighted graph (host CSR without a diagonal,
+ * columns strictly ascending within a row, (i, j) and (j, i) the same bits: what scc_snn_graph
+ * and scc_umap_graph return).  Weights enter as q = (int64)rint(w 2^32); an entry with q = 0 is
+ * absent.  m2 = sum q.  One level on a graph whose vertex degrees k_i are the row sums (a coarse
+ * level's self-loop included): every vertex starts in its own community; sweeps are synchronous,
+ * each reading the previous sweep's communities, totals tot_c and sizes.  For vertex i in c_i
+ * the candidates are c_i and the communities of its neighbours j != i:
+ *   kin(c) = sum of q_ij over j in c, j != i;  t = tot_c - (c == c_i ? k_i : 0)
+ *   g(c)   = (double)kin - ((resolution (double)k_i) (double)t) / (double)m2, in that order
+ * c* has the largest g, ties to the smallest id; i moves iff c* != c_i, g(c*) > g(c_i) and not
+ * (both communities have one member and c* > c_i).  No move: the level ends.  Else
+ * Q = sum over community ids c = 0 .. (the level's vertices - 1) of
+ * (double)in_c / m2 - (resolution ((double)tot_c / m2)) ((double)tot_c / m2) (in_c: every entry
+ * inside c; an id without members gives 0), summed as thread t of 1024 adds terms t, t + 1024,
+ * ... and a halving tree follows; Q <= the previous Q: the sweep is discarded and the level
+ * ends.  At most 256 sweeps a level.  Then the communities with members are renumbered in
+ * ascending id and become the next level's vertices (integer sums of the entries, the
+ * self-loop all entries inside; m2 is kept); levels repeat until one merges nothing, at most
+ * SCC_MODULARITY_MAX_LEVELS.  A graph without weight (m2 = 0) is left as n clusters, 0 levels.
+ * labels: host [n], numbered by (size descending, smallest member ascending): 0 is the largest.
+ * modularity: the last accepted Q (level 0's initial Q if none).  n_levels: levels run, the
+ * last one that merged nothing included.  sweeps: host [SCC_MODULARITY_MAX_LEVELS], the sweeps
+ * run in each level (a discarded or moveless last one included), 0 beyond n_levels.  Each of
+ * n_clusters, modularity, n_levels, sweeps may be NULL.
+ *   SCC_ERR_INVALID      n < 1, an inconsistent CSR (indptr, a column outside 0..n-1, columns
+ *                        not ascending), a diagonal entry, a negative weight, a missing or
+ *                        differing transpose entry, resolution <= 0
+ *   SCC_ERR_NONFINITE    a non-finite weight or resolution
+ *   SCC_ERR_UNSUPPORTED  a weight above 2^20, or m2 >= 2^62
+ * All checked before anything is uploaded.  Timer family "modularity_cluster", one entry per
+ * call. */
+#define SCC_MODULARITY_MAX_LEVELS 32
+SCC_API int scc_modularity_cluster(scc_ctx* ctx, int64_t n, const int64_t* indptr /* host [n + 1] */,
+                                   const int32_t* cols, const double* vals, double resolution,
+                                   int32_t* labels /* host [n] */, int32_t* n_clusters, double* modularity,
+                                   int32_t* n_levels, int32_t* sweeps);
+/* scc_knn_scores (k = k_param - 1, same scores, dims and refusals), scc_snn_graph and
+ * scc_modularity_cluster in one call without the table or the graph leaving the device: bit
+ * for bit what the three calls return one after the other.  k_param in 2..SCC_KNN_MAX_K + 1 and
+ * at most n.  Only the labels cross to the host, and the graph when indptr, cols and vals are
+ * given (cap, nnz: as scc_snn_graph; all three NULL: no graph is copied, *nnz is still set).
+ * Timer families "knn_scores", "snn_graph" and "modularity_cluster", one entry per call each. */
+SCC_API int scc_snn_clusters_scores(scc_ctx* ctx, int64_t n, const void* scores /* device [n][16], NULL = kept */,
+                                    int32_t dims /* 1..15, 0 = all */, int32_t k_param, double prune,
+                                    double resolution, int32_t* labels /* host [n] */, int32_t* n_clusters,
+                                    double* modularity, int32_t* n_levels, int32_t* sweeps, int64_t* indptr,
+                                    int32_t* cols, double* vals, int64_t cap, int64_t* nnz);
+
 /* ---- heatmap inputs (cellTypeDEPlot.R:168-253) ---------------------------
  * What both reference functions end with (Fast:456-464, slow:288-296):
  * cellTypeDEPlot(dataMatrix[deGeneUnion, ], ...) hands the |U| x N block to

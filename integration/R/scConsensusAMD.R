@@ -253,6 +253,35 @@ sccUmap <- function(dataMatrix, genes, n_neighbors = 15, n = 15, dims = 8, n_epo
   layout
 }
 
+# ---- SNN graph and modularity clustering on the engine -------------------------
+# The step in front of the README's example: its seuratObj$RNA_snn_res.0.2 is what
+# Seurat's FindNeighbors + FindClusters make of the PCA scores.  One engine call
+# (C_scc_find_clusters: the PCA, the exact neighbour search, the SNN graph by
+# Seurat's ComputeSNN rule and a deterministic multilevel modularity clustering;
+# the table and the graph stay on the device).  Returns a factor of cluster labels
+# named by cell, "0" the largest cluster as in Seurat, ready for
+# plotContingencyTable and reclusterDEConsensusFast; attributes "modularity" and
+# "sweeps".  The rules are restated in tests/snn_reference.py; the result has not
+# been compared with Seurat (it was not at hand), and there is no Leiden or SLM
+# refinement, no grouping of singletons and no random vertex order.
+#   k.param     counts the cell itself, as FindNeighbors' k.param does (2..65)
+#   prune.SNN   pairs whose shared-neighbour weight is below it are dropped
+sccFindClusters <- function(dataMatrix, genes, k.param = 20, n = 15, dims = n, prune.SNN = 1 / 15, resolution = 0.8) {
+  rows <- if (is.character(genes)) match(genes, rownames(dataMatrix)) else as.integer(genes)
+  if (anyNA(rows)) stop("sccFindClusters: a gene is not a row of the matrix")
+  if (k.param < 2L) stop("sccFindClusters: k.param leaves no neighbour besides the cell itself")
+  if (dims < 1L || dims > n) stop("sccFindClusters: dims must lie in 1..n")
+  h <- .scc_dataset(dataMatrix)
+  on.exit(.Call("C_scc_release", h), add = TRUE)
+  res <- .Call("C_scc_find_clusters", h, as.integer(rows), as.integer(n), as.integer(dims), as.integer(k.param),
+               as.numeric(c(prune.SNN, resolution)))
+  labels <- factor(res[[1]], levels = seq_len(max(res[[1]]) + 1L) - 1L)
+  names(labels) <- colnames(dataMatrix)
+  attr(labels, "modularity") <- res[[2]]
+  attr(labels, "sweeps") <- res[[3]]
+  labels
+}
+
 # The drawing for options(scConsensus.engineHeatmapRows = TRUE): the wrapper's
 # own plotting helper, written from ComplexHeatmap's documented arguments.  Rows
 # follow the engine's tree (cluster_rows = a dendrogram, row_dend_reorder =

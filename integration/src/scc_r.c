@@ -38,6 +38,8 @@
  *                   PCA scores, the search umap(d = pca.data) starts with
  *   C_scc_umap      sccUmap: that search, UMAP's fuzzy simplicial set and its
  *                   layout from the PCA scores in one engine call
+ *   C_scc_find_clusters  sccFindClusters: that search, the SNN graph and a
+ *                   modularity clustering from the PCA scores in one engine call
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -582,6 +584,41 @@ SEXP C_scc_umap(SEXP h, SEXP genes, SEXP ncomp, SEXP dims, SEXP n_neighbors, SEX
     return out;
 }
 
+/* sccFindClusters: the PCA of C_scc_pca_scores, then scc_snn_clusters_scores on
+ * the kept scores (the neighbour search, the SNN graph and the modularity
+ * clustering without the table or the graph leaving the device).  par:
+ * numeric(2) = prune, resolution.  Returns list(labels = integer(N), 0-based
+ * with 0 the largest cluster, modularity, sweeps = the sweeps run per level). */
+SEXP C_scc_find_clusters(SEXP h, SEXP genes, SEXP ncomp, SEXP dims, SEXP k_param, SEXP par)
+{
+    ensure_ctx();
+    int G = 0, N = 0;
+    scc_dataset* ds = ds_of(h, &G, &N);
+    const int nu = LENGTH(genes), kp = Rf_asInteger(k_param);
+    int32_t* g0 = (int32_t*)R_alloc((size_t)nu, sizeof(int32_t));
+    for (int q = 0; q < nu; ++q) {
+        g0[q] = INTEGER(genes)[q] - 1;
+        if (g0[q] < 0 || g0[q] >= G) Rf_error("scConsensus engine: gene row %d out of range", g0[q] + 1);
+    }
+    if (kp < 2 || kp > N) Rf_error("scConsensus engine: k.param = %d of %d cells", kp, N);
+    if (LENGTH(par) < 2) Rf_error("scConsensus engine: C_scc_find_clusters needs 2 parameters");
+    check(scc_pca_scores(g_ctx, ds, g0, nu, Rf_asInteger(ncomp)));
+    SEXP labels = PROTECT(Rf_allocVector(INTSXP, N));
+    int32_t n_clusters = 0, n_levels = 0, sweeps[SCC_MODULARITY_MAX_LEVELS];
+    double q = 0.0;
+    check(scc_snn_clusters_scores(g_ctx, N, NULL, Rf_asInteger(dims), kp, REAL(par)[0], REAL(par)[1],
+                                  (int32_t*)INTEGER(labels), &n_clusters, &q, &n_levels, sweeps, NULL, NULL, NULL, 0,
+                                  NULL));
+    SEXP sw = PROTECT(Rf_allocVector(INTSXP, n_levels));
+    for (int l = 0; l < n_levels; ++l) INTEGER(sw)[l] = sweeps[l];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, labels);
+    SET_VECTOR_ELT(out, 1, Rf_ScalarReal(q));
+    SET_VECTOR_ELT(out, 2, sw);
+    UNPROTECT(3);
+    return out;
+}
+
 /* hclust(dist(scores), "ward.D2") from the engine-kept scores of n cells
  * (scc_hclust_ward_d2_scores: no N x N matrix anywhere) */
 SEXP C_scc_hclust_scores(SEXP n_cells)
@@ -688,6 +725,7 @@ static const R_CallMethodDef call_methods[] = {
     {"C_scc_si_scores", (DL_FUNC)&C_scc_si_scores, 1},
     {"C_scc_knn", (DL_FUNC)&C_scc_knn, 5},
     {"C_scc_umap", (DL_FUNC)&C_scc_umap, 7},
+    {"C_scc_find_clusters", (DL_FUNC)&C_scc_find_clusters, 6},
     {NULL, NULL, 0}};
 
 /* the package is scConsensus (NAMESPACE: useDynLib(scConsensus, .registration = TRUE)) */

@@ -52,6 +52,7 @@ EXPORTS = [
     "scc_hclust_ward_d2", "scc_cutree_hybrid", "scc_hclust_ward_d2_dev", "scc_cutree_hybrid_dev",
     "scc_pca_scores", "scc_hclust_ward_d2_scores", "scc_cutree_hybrid_scores", "scc_silhouette_scores",
     "scc_knn_scores", "scc_umap_graph", "scc_umap_layout", "scc_umap_scores",
+    "scc_snn_graph", "scc_modularity_cluster", "scc_snn_clusters_scores",
     "scc_gene_distance", "scc_hclust_complete", "scc_dendro_reorder", "scc_heatmap_raster",
     "scc_diag_eigen_topk", "scc_diag_small_syev", "scc_diag_cholinv", "scc_diag_eig_last_path",
     "scc_diag_ingest_last_path", "scc_diag_rank_last_route", "scc_diag_rank_last_runs", "scc_diag_mirror_last_uses", "scc_diag_hclust_last_scans",
@@ -90,6 +91,8 @@ class UmapParams(ctypes.Structure):
                 ("gamma", ctypes.c_double), ("learning_rate", ctypes.c_double), ("seed", ctypes.c_uint64),
                 ("reserved", ctypes.c_int32 * 4)]
 
+
+MODULARITY_MAX_LEVELS = 32  # scc.h: SCC_MODULARITY_MAX_LEVELS
 
 # find_ab_params(spread = 1, min_dist = 0.1) (scc.h: SCC_UMAP_A, SCC_UMAP_B)
 UMAP_A = 1.5769434602697652
@@ -185,6 +188,10 @@ def load():
         "scc_umap_graph": (ctypes.c_int, [vp, i64, i32, vp, vp, P(UmapParams), vp, vp, vp, i64, P(i64), vp, vp, vp]),
         "scc_umap_layout": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, P(UmapParams), vp]),
         "scc_umap_scores": (ctypes.c_int, [vp, i64, vp, i32, i32, P(UmapParams), vp, vp, vp, vp, vp, i64, P(i64)]),
+        "scc_snn_graph": (ctypes.c_int, [vp, i64, i32, vp, dbl, vp, vp, vp, vp, i64, P(i64)]),
+        "scc_modularity_cluster": (ctypes.c_int, [vp, i64, vp, vp, vp, dbl, vp, P(i32), P(dbl), P(i32), vp]),
+        "scc_snn_clusters_scores": (ctypes.c_int, [vp, i64, vp, i32, i32, dbl, dbl, vp, P(i32), P(dbl), P(i32), vp, vp,
+                                                   vp, vp, i64, P(i64)]),
         "scc_gene_distance": (ctypes.c_int, [vp, vp, vp, i32, vp, vp, vp]),
         "scc_hclust_complete": (ctypes.c_int, [vp, i64, vp, vp, vp]),
         "scc_dendro_reorder": (ctypes.c_int, [vp, i64, vp, vp, vp]),
@@ -813,6 +820,90 @@ class Engine:
         if return_graph:
             return Y, (indptr, cols[:nnz.value].copy(), vals[:nnz.value].copy())
         return Y
+
+    # -------------------------------------------------------------- SNN graph and clustering
+    def snn_graph(self, idx, prune=1.0 / 15.0, return_shared=False, cap=None):
+        """The shared-nearest-neighbour graph of a k-NN table in knn_scores'
+        output form (Seurat's ComputeSNN rule, k.param = k + 1, the diagonal
+        not stored): the symmetric CSR (indptr int64 [N + 1], cols int32, vals
+        float64), columns ascending within a row; with return_shared also the
+        shared counts (int32, parallel to vals).  The entries have no bound
+        such as 2 N k: a first call that finds its buffers too small is
+        repeated with the size it reported (cap given: one call with buffers
+        of cap entries, refused when they are too small)."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        if idx.ndim != 2:
+            raise ValueError("idx must be an [N, k] array")
+        N, k = idx.shape
+        indptr = np.zeros(N + 1, np.int64)
+        nnz = ctypes.c_int64()
+        retry = cap is None
+        cap = max(4 * N * (k + 1), 1) if retry else max(int(cap), 1)
+        while True:
+            cols, vals, shared = np.empty(cap, np.int32), np.empty(cap), np.empty(cap, np.int32)
+            rc = self.lib.scc_snn_graph(self.ctx, N, k, _ptr(idx), float(prune), _ptr(indptr), _ptr(cols), _ptr(vals),
+                                        _ptr(shared), cap, ctypes.byref(nnz))
+            if retry and rc == SCC_ERR_INVALID and nnz.value > cap:
+                cap, nnz.value = nnz.value, 0
+                continue
+            self._check(rc)
+            break
+        g = (indptr, cols[:nnz.value].copy(), vals[:nnz.value].copy())
+        return g + (shared[:nnz.value].copy(),) if return_shared else g
+
+    def modularity_cluster(self, indptr, cols, vals, resolution=1.0):
+        """Deterministic multilevel modularity clustering of a symmetric
+        weighted CSR graph (snn_graph's or umap_graph's output form): a dict
+        of labels (int32 [N], 0 the largest cluster), n_clusters, modularity,
+        n_levels and sweeps (the sweeps run in each level)."""
+        indptr = np.ascontiguousarray(indptr, np.int64)
+        cols = np.ascontiguousarray(cols, np.int32)
+        vals = np.ascontiguousarray(vals, np.float64)
+        N = len(indptr) - 1
+        if N < 1 or cols.shape != vals.shape or cols.ndim != 1:
+            raise ValueError("modularity_cluster: indptr [N + 1], cols and vals of one length")
+        if len(cols) < indptr[-1]:
+            raise ValueError("modularity_cluster: cols and vals are shorter than indptr[-1]")
+        labels = np.empty(N, np.int32)
+        nc, nl, q = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        sweeps = np.zeros(MODULARITY_MAX_LEVELS, np.int32)
+        self._check(self.lib.scc_modularity_cluster(self.ctx, N, _ptr(indptr), _ptr(cols), _ptr(vals),
+                                                    float(resolution), _ptr(labels), ctypes.byref(nc),
+                                                    ctypes.byref(q), ctypes.byref(nl), _ptr(sweeps)))
+        return {"labels": labels, "n_clusters": nc.value, "modularity": q.value, "n_levels": nl.value,
+                "sweeps": sweeps[:nl.value].tolist()}
+
+    def snn_clusters_scores(self, N, k_param=20, dims=0, prune=1.0 / 15.0, resolution=0.8, scores_device_ptr=None,
+                            return_graph=False):
+        """knn_scores (k = k_param - 1), snn_graph and modularity_cluster in
+        one call on a device [N][16] score matrix (same rule as knn_scores),
+        the table and the graph staying on the device: modularity_cluster's
+        dict, bit for bit what the three calls give; with return_graph also
+        "graph", the SNN CSR triple."""
+        N, kp = int(N), int(k_param)
+        labels = np.empty(max(N, 1), np.int32)
+        nc, nl, q = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        sweeps = np.zeros(MODULARITY_MAX_LEVELS, np.int32)
+        nnz = ctypes.c_int64()
+        indptr = cols = vals = None
+        cap = max(4 * N * max(kp, 1), 1) if return_graph else 0
+        while True:
+            if return_graph:
+                indptr, cols, vals = np.zeros(max(N, 0) + 1, np.int64), np.empty(cap, np.int32), np.empty(cap)
+            rc = self.lib.scc_snn_clusters_scores(self.ctx, N, ctypes.c_void_p(scores_device_ptr or None), int(dims), kp,
+                                                  float(prune), float(resolution), _ptr(labels), ctypes.byref(nc),
+                                                  ctypes.byref(q), ctypes.byref(nl), _ptr(sweeps), _ptr(indptr),
+                                                  _ptr(cols), _ptr(vals), cap, ctypes.byref(nnz))
+            if return_graph and rc == SCC_ERR_INVALID and nnz.value > cap:
+                cap, nnz.value = nnz.value, 0
+                continue
+            self._check(rc)
+            break
+        out = {"labels": labels[:N], "n_clusters": nc.value, "modularity": q.value, "n_levels": nl.value,
+               "sweeps": sweeps[:nl.value].tolist(), "nnz": nnz.value}
+        if return_graph:
+            out["graph"] = (indptr, cols[:nnz.value].copy(), vals[:nnz.value].copy())
+        return out
 
     # -------------------------------------------------------------- heatmap inputs
     def gene_distance(self, ds: Dataset, genes):

@@ -551,3 +551,49 @@ def umap(dataMatrix, genes, n_neighbors=15, ncomp=15, dims=None, n_epochs=200, m
     finally:
         ds.close()
     return {"layout": out[0], "graph": out[1]} if return_graph else {"layout": out, "graph": None}
+
+
+def find_clusters(dataMatrix, genes, k_param=20, ncomp=15, dims=None, prune=1.0 / 15.0, resolution=0.8,
+                  return_graph=False, device=0, *, gene_names=None):
+    """The step in front of the reference README's example: its
+    ``seuratObj$RNA_snn_res.0.2`` is what Seurat's ``FindNeighbors`` +
+    ``FindClusters`` make of the PCA scores.  On the engine: the PCA of the
+    gene rows, the exact neighbour search, the shared-nearest-neighbour graph
+    (Seurat's ComputeSNN rule) and a deterministic multilevel modularity
+    clustering (scc_pca_scores, scc_snn_clusters_scores) without the table or
+    the graph leaving the device.  The rules are restated in
+    tests/snn_reference.py; agreement with Seurat has not been measured, and
+    there is no Leiden or SLM refinement, no grouping of singletons and no
+    random vertex order.
+
+    genes, ncomp, dims, gene_names: as ``nearest_neighbors``.  k_param counts
+    the cell itself (2..65).  Returns ``{"labels": int32 [N] (0 the largest
+    cluster; ``reclusterDEConsensusFast`` takes them as they are),
+    "n_clusters", "modularity", "n_levels", "sweeps", "graph": (indptr, cols,
+    vals) or None}``, the graph only with ``return_graph``."""
+    g = np.asarray(genes)
+    if g.dtype.kind in "USO":
+        if gene_names is None:
+            raise ValueError("genes given by name need gene_names")
+        pos = {name: r for r, name in enumerate(gene_names)}
+        try:
+            g = np.array([pos[name] for name in g], np.int32)
+        except KeyError as e:
+            raise ValueError(f"unknown gene {e.args[0]!r}") from None
+    g = np.ascontiguousarray(g, np.int32)
+    k_param, ncomp = int(k_param), int(ncomp)
+    dims = ncomp if dims is None else int(dims)
+    if not 1 <= dims <= ncomp:
+        raise ValueError("dims must lie in 1..ncomp")
+    if k_param < 2:
+        raise ValueError("k_param leaves no neighbour besides the cell itself")
+    eng = _engine(device)
+    ds = _upload(eng, _as_matrix(dataMatrix))
+    try:
+        eng.pca_scores(ds, g, ncomp)
+        out = eng.snn_clusters_scores(ds.N, k_param, dims, prune, resolution, None, return_graph=bool(return_graph))
+    finally:
+        ds.close()
+    out.setdefault("graph", None)
+    out.pop("nnz", None)
+    return out
